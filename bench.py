@@ -36,9 +36,10 @@ Per rank (one process per MI355X, RCCL over xGMI when N > 1):
      The throughput drains of the columnar engine and of both groups run three times and report
      the median (``..._runs_dialogues_per_s`` lists all three: a sub-second drain of Python clients
      on a shared host moves by +-15 % from run to run, profiles/r6/kafka/NOTES.md).
-Phases 3 and 4 run after the headline (1, 2 and the single-dialogue latency) is measured, each
-under a PhaseGuard: a failure is reported as ``rf_error`` / ``kafka_error`` in the record and a
-hang is cut off after ``--phase-timeout`` s with the record printed as it stands.
+A plain run does phases 1 and 2 only (the headline: the streaming steps score with the model that
+phase 1 trained) and prints the record. ``--full`` adds the single-dialogue latency and phases 3
+and 4, which run after the headline is measured, each under a PhaseGuard: a failure is reported
+as ``rf_error`` / ``kafka_error`` in the record and a hang is cut off after ``--phase-timeout`` s with the record printed as it stands.
 Data is synthetic (the reference dataset is not available) with random-init-free trained trees.
 Before the timed training, an untimed 2-tree fit on 65,536 rows loads the kernels' code objects
 (lazily loaded on first launch by ROCm) and warms the allocators (``gbdt_warmup_sec_untimed``).
@@ -47,7 +48,13 @@ from the all-reduced max, accumulated as int64 by LDS atomics in the row-group k
 csrc/row_kernels.hip) — at least fp32-accurate and bitwise reproducible; gains, leaves and scores
 are fp64; text is bytes. Reported as "fp32".
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+``--dump-outputs DIR`` writes what the last timed streaming step delivered to the host, one
+``DIR/<name>.npy`` (float64) per array: ``scores`` (the kernel's raw tree sums), ``prediction`` and
+``probability``, each of ``--batch`` rows (rank r > 0 of a multi-rank run writes ``<name>.rank<r>.npy``).
+The corpus, the trained model and the micro-batches are seeded and the training is bitwise
+reproducible, so two runs with the same arguments score identical inputs.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver via torch.distributed.run (RANK/WORLD_SIZE/MASTER_* in env).
 """
 from __future__ import annotations
@@ -450,6 +457,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the single-dialogue latency, RandomForest training (phase 3) and Kafka end "
+                         "to end (phase 4); a plain run stops after the streaming steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed streaming step to DIR/<name>.npy")
     ap.add_argument("--rows", type=int, default=10_000_000, help="GBDT training rows (total over ranks)")
     ap.add_argument("--trees", type=int, default=100)
     ap.add_argument("--depth", type=int, default=6)
@@ -499,7 +511,7 @@ def main():
     # ------------------------------------------------------------------ 1. GBDT training
     gparams = GBDTParams(n_estimators=args.trees, max_depth=args.depth, max_bin=cfg.gbdt_max_bin)
     t0 = time.perf_counter()
-    warmup_training(dev, spec, gparams, args.rf_depth if args.rf_trees > 0 else 0)
+    warmup_training(dev, spec, gparams, args.rf_depth if args.full and args.rf_trees > 0 else 0)
     warm_sec = time.perf_counter() - t0
     lo, hi = D.shard_range(args.rows)
     t0 = time.perf_counter()
@@ -555,16 +567,19 @@ def main():
     def run(steps: int, check: bool):
         """Every step delivers (prediction, P(scam)) for a micro-batch to the host. Accuracy
         against the synthetic labels is only tallied in the (untimed) warmup pass."""
-        correct = total = 0
+        correct = total = done = 0
         sink = 0.0
 
         def finish():
-            nonlocal correct, total, sink
+            nonlocal correct, total, sink, done
             a = time.perf_counter()
             slot, raw = scorer.collect(copy=False)
             b = time.perf_counter()
             pred, p = model.postprocess_numpy(raw)
             sink += float(p[0])
+            done += 1
+            if done == steps:          # the last step's outputs (raw is a view of the pinned result slot)
+                last.update(scores=raw.copy(), prediction=pred, probability=p)
             if check:
                 correct += int((pred == pool_labels[slot.index]).sum())
                 total += len(pred)
@@ -582,6 +597,7 @@ def main():
         return correct, total
 
     timing = {"collect": 0.0, "post": 0.0, "submit": 0.0}
+    last = {}
 
     correct, total = run(max(args.warmup, len(ring.slots)), True)
     sync_all(dev)
@@ -594,23 +610,31 @@ def main():
               file=sys.stderr, flush=True)
     dt = max_over_ranks(time.perf_counter() - t0, dev)
     acc = correct / max(total, 1)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in last.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"),
+                    np.ascontiguousarray(a, dtype=np.float64))
 
-    # single-dialogue end-to-end classify latency (unpipelined: H2D + kernel + D2H + postprocess)
-    one = PinnedRing(slots=1, max_docs=1, max_bytes=8192)
-    lat_scorer = GpuScorer(spec, idf_np, model.scorer(), dev, max_docs=1, max_bytes=8192, depth=1)
-    text = ring.slots[0]
-    first = bytes(text.data[: int(text.offsets[1])].numpy()).decode()
-    one.slots[0].fill([first])
-    lats = []
-    for _ in range(60):
-        t1 = time.perf_counter()
-        raw = lat_scorer.score_packed(one.slots[0])
-        model.postprocess_numpy(raw)
-        lats.append((time.perf_counter() - t1) * 1e3)
-    p50 = float(np.percentile(lats[10:], 50))
-    del scorer, lat_scorer
+    def single_dialogue_p50() -> float:
+        """Single-dialogue end-to-end classify latency (unpipelined: H2D + kernel + D2H + postprocess)."""
+        one = PinnedRing(slots=1, max_docs=1, max_bytes=8192)
+        lat_scorer = GpuScorer(spec, idf_np, model.scorer(), dev, max_docs=1, max_bytes=8192, depth=1)
+        text = ring.slots[0]
+        first = bytes(text.data[: int(text.offsets[1])].numpy()).decode()
+        one.slots[0].fill([first])
+        lats = []
+        for _ in range(60):
+            t1 = time.perf_counter()
+            raw = lat_scorer.score_packed(one.slots[0])
+            model.postprocess_numpy(raw)
+            lats.append((time.perf_counter() - t1) * 1e3)
+        return float(np.percentile(lats[10:], 50))
 
-    # the headline record is complete here: the phases below only add to it, each one isolated
+    p50 = single_dialogue_p50() if args.full else None
+    del scorer
+
+    # the headline record is complete here: the phases below (--full) only add to it, each one isolated
     # (an error lands in the record as <phase>_error; a phase that hangs past --phase-timeout is
     # cut off by the watchdog, which prints the record as it stands)
     gbdt_peak_gb = max_over_ranks(gbdt_peak / 2 ** 30, dev)
@@ -642,12 +666,13 @@ def main():
         "datagen_peak_hbm_gb_untimed": gen_peak_gb,
         **sizing,
         "stream_accuracy": acc,
-        "p50_single_dialogue_ms": p50,
         "numa_bind_rank0": numa,
     }
+    if args.full:
+        record["p50_single_dialogue_ms"] = p50
     guard = PhaseGuard(record, rank, args.phase_timeout)
 
-    if args.rf_trees > 0:
+    if args.full and args.rf_trees > 0:
         # ------------------------------------------------------------------ 3. RandomForest
         def rf_phase():
             torch.cuda.empty_cache()
@@ -666,7 +691,7 @@ def main():
     del vc, indptr, idx, counts, y, fo
     torch.cuda.empty_cache()
 
-    if args.kafka_msgs > 0:
+    if args.full and args.kafka_msgs > 0:
         # ------------------------------------------------------------------ 4. Kafka end to end
         def kafka_run():
             kafka = kafka_phase(args, spec, idf_np, model, dev, rank)

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for rep in 1 2; do
   for ms in 1.0 0.5; do
-    timeout -k 10 240 python -u bench.py --rows 1000000 --rf-trees 0 --steps 10 --kafka-fill-ms $ms \
+    timeout -k 10 240 python -u bench.py --full --rows 1000000 --rf-trees 0 --steps 10 --kafka-fill-ms $ms \
       > "$OUT/b_${ms}_$rep.json" 2> "$OUT/b_${ms}_$rep.err"
     python - "$ms" "$OUT/b_${ms}_$rep.json" <<'PY' | tee -a "$OUT/summary.jsonl"
 import json, sys

@@ -23,7 +23,7 @@ export TMPDIR=/tmp
 cat "$OUT/topology.txt"
 run() {
   local name=$1; shift
-  env "$@" timeout -k 10 240 python -u bench.py --rows 1000000 --rf-trees 0 --steps 10 \
+  env "$@" timeout -k 10 240 python -u bench.py --full --rows 1000000 --rf-trees 0 --steps 10 \
     > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"
   python - "$name" "$OUT/bench_$name.json" <<'EOF' | tee -a "$OUT/summary.jsonl"
 import json, sys

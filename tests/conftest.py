@@ -8,8 +8,8 @@ REPO = Path(__file__).resolve().parents[1]
 if str(REPO) not in sys.path:
     sys.path.insert(0, str(REPO))
 
-REFERENCE = Path("/root/reference")
-SHIPPED_MODEL = REFERENCE / "dialogue_classification_model"
+# the reference's shipped Spark PipelineModel (metadata JSON + parquet + CRCs, ~140 KB), stored as data
+SHIPPED_MODEL = REPO / "tests" / "golden" / "dialogue_classification_model"
 
 
 def pytest_configure(config):
@@ -30,14 +30,13 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope="session")
 def shipped_model_path():
-    if not SHIPPED_MODEL.exists():
-        pytest.skip("reference model not mounted")
+    assert SHIPPED_MODEL.is_dir(), f"{SHIPPED_MODEL} is part of the repository"
     return SHIPPED_MODEL
 
 
 @pytest.fixture(scope="session")
 def scam_sample():
-    """The commented-out usage-example dialogue (/root/reference/utils/agent_api.py:224)."""
+    """The commented-out usage-example dialogue of the reference (utils/agent_api.py:224)."""
     from fraud_detection_spark_kafka_llm_amd.data.fixtures import SCAM_SAMPLE
 
     return SCAM_SAMPLE

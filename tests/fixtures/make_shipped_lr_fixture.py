@@ -1,8 +1,8 @@
 """Regenerate ``shipped_lr.npz`` from the reference's shipped ``dialogue_classification_model``.
 
-The GPU box has no /root/reference, so the golden-value tests there run on the shipped model's
-arrays (coefficients, intercept, IDF, HashingTF width, stop words, column names) saved as a plain
-npz (no pickle), read back by ``tests/shipped_model.py``. Run here with the reference mounted:
+The golden-value tests run on the shipped model's arrays (coefficients, intercept, IDF, HashingTF
+width, stop words, column names) saved as a plain npz (no pickle), read back by
+``tests/shipped_model.py``. The model itself is stored under ``tests/golden/``:
 ``python tests/fixtures/make_shipped_lr_fixture.py``.
 """
 import json
@@ -17,7 +17,7 @@ sys.path.insert(0, str(ROOT))
 from fraud_detection_spark_kafka_llm_amd.ml import PipelineModel  # noqa: E402
 
 
-def main(src="/root/reference/dialogue_classification_model", out=Path(__file__).with_name("shipped_lr.npz")):
+def main(src=ROOT / "tests" / "golden" / "dialogue_classification_model", out=Path(__file__).with_name("shipped_lr.npz")):
     pm = PipelineModel.load(src)
     tok, sw, tf, idf, lr = pm.stages
     cols = {"tok": [tok.getInputCol(), tok.getOutputCol()], "sw": [sw.getInputCol(), sw.getOutputCol()],

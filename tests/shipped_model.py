@@ -1,5 +1,5 @@
 """The reference's shipped LR pipeline rebuilt from ``fixtures/shipped_lr.npz`` (see
-fixtures/make_shipped_lr_fixture.py): usable where /root/reference is not mounted (GPU box)."""
+fixtures/make_shipped_lr_fixture.py): the model's arrays without the Spark directory layout."""
 import json
 from pathlib import Path
 

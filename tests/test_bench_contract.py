@@ -11,7 +11,9 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config"}
-TINY = ["--steps", "4", "--warmup", "2", "--rows", "100000", "--trees", "3", "--batch", "4096", "--pool", "2",
+SMALL = ["--steps", "4", "--warmup", "2", "--rows", "100000", "--trees", "3", "--batch", "4096", "--pool", "2"]
+# every phase (--full: single-dialogue latency, RandomForest, Kafka), at small sizes
+TINY = ["--full", "--steps", "4", "--warmup", "2", "--rows", "100000", "--trees", "3", "--batch", "4096", "--pool", "2",
         "--rf-trees", "4", "--kafka-msgs", "20000", "--kafka-sec", "0.5", "--kafka-multi-msgs", "20000",
         "--kafka-confluent-msgs", "5000", "--kafka-confluent-rate", "5000", "--kafka-group-msgs", "20000",
         "--kafka-group-rate", "6000"]
@@ -45,6 +47,27 @@ def test_bench_single_gpu_contract():
                          timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     _check(_json_line(out.stdout), 1)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full: GBDT train + the timed streaming steps, one record with the contract keys and
+    none of the later phases; --dump-outputs writes the last timed step's arrays as float64 .npy."""
+    import numpy as np
+
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *SMALL, "--dump-outputs", str(tmp_path / "o")],
+                         cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = _json_line(out.stdout)
+    assert KEYS <= set(rec) and rec["steps"] == 4 and rec["value"] > 0 and rec["gbdt_train_sec"] > 0
+    assert rec["value"] == pytest.approx(4 * 4096 / (rec["ms_per_step"] * 4e-3))
+    assert rec["stream_accuracy"] > 0.9
+    assert not [k for k in rec if k.startswith(("rf_", "kafka_", "p50_"))]
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["prediction.npy", "probability.npy", "scores.npy"]
+    arr = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in ("prediction", "probability", "scores")}
+    assert all(a.dtype == np.float64 and a.shape[0] == 4096 and np.isfinite(a).all() for a in arr.values())
+    assert set(np.unique(arr["prediction"])) <= {0.0, 1.0} and 0 < arr["prediction"].mean() < 1
+    assert np.array_equal(arr["prediction"], (arr["probability"] > 0.5).astype(np.float64))
 
 
 @pytest.mark.gpu
