@@ -111,6 +111,118 @@ struct Rccl {
   }
 };
 
+// The level collectives of a data-parallel runner (RfLevels' GBDT levels, RfBatch), on the level's
+// stream: RCCL itself when the process group's communicator is reachable (direct), else Python
+// callbacks (the process group's collectives on the current stream). The runners' level loops may
+// run with the GIL released, so every callback takes it, its result's cast included.
+struct DpComm {
+  Rccl rccl;
+  bool direct = false;
+  py::object rs_cb, ag_cb, max_cb;
+  int64_t calls[3] = {0, 0, 0};           // reduce-scatters, all-gathers, all-reduces since they restarted
+  int64_t timed = 0;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> timing;
+
+  DpComm() = default;
+  DpComm(const DpComm&) = delete;
+  DpComm& operator=(const DpComm&) = delete;
+  ~DpComm() {
+    for (auto& e : timing) {
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+  }
+
+  // callbacks rs / ag (/ mx: the all-reduce, where the runner has one), communicator comm + rccl_lib
+  void setup(const py::dict& c) {
+    rs_cb = c["rs"];
+    ag_cb = c["ag"];
+    if (c.contains("mx")) max_cb = c["mx"];
+    direct = c.contains("comm") && !c["comm"].is_none() &&
+             rccl.load(c["rccl_lib"].cast<std::string>(), c["comm"].cast<int64_t>());
+  }
+
+  // timing events around every 8th direct collective (ms)
+  struct Timer {
+    DpComm* c;
+    hipStream_t s;
+    hipEvent_t b = nullptr;
+    Timer(DpComm* c_, hipStream_t s_) : c(c_), s(s_) {
+      if ((c->timed++ & 7) == 0 && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(b, s);
+    }
+    ~Timer() {
+      hipEvent_t e = nullptr;
+      if (b && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, s) == hipSuccess) c->timing.emplace_back(b, e);
+    }
+  };
+
+  void reduce_scatter(const Tensor& send, const Tensor& out, hipStream_t s) {
+    ++calls[0];
+    if (!direct) {
+      py::gil_scoped_acquire gil;
+      rs_cb(send, out);
+      return;
+    }
+    Timer t(this, s);
+    rccl.check(rccl.rs(send.data_ptr(), out.data_ptr(), (size_t)out.numel(), ncclInt64, ncclSum, rccl.comm, s),
+               "ncclReduceScatter");
+  }
+
+  // in [n, 5] of every rank as [S, n, 5]: gathered into out; without an out buffer (callbacks only)
+  // the callback's own result, with one its result copied there on the stream
+  Tensor all_gather(const Tensor& in, const Tensor& out, hipStream_t s) {
+    ++calls[1];
+    if (!direct) {
+      Tensor r;
+      {
+        py::gil_scoped_acquire gil;
+        r = ag_cb(in).cast<Tensor>();
+      }
+      if (!out.defined()) return r;
+      FDX_CHECK(r.numel() == out.numel(), "all-gather callback result size");
+      out.copy_(r.view_as(out));
+      return out;
+    }
+    Timer t(this, s);
+    rccl.check(rccl.ag(in.data_ptr(), out.data_ptr(), (size_t)in.numel(), ncclInt64, rccl.comm, s), "ncclAllGather");
+    return out;
+  }
+
+  void all_reduce_max(const Tensor& buf, hipStream_t s) {
+    ++calls[2];
+    if (!direct) {
+      py::gil_scoped_acquire gil;
+      max_cb(buf);
+      return;
+    }
+    Timer t(this, s);
+    rccl.check(rccl.ar(buf.data_ptr(), buf.data_ptr(), (size_t)buf.numel(), ncclInt64, ncclMax, rccl.comm, s),
+               "ncclAllReduce");
+  }
+
+  // Milliseconds of the direct collectives timed since the last call (every 8th, scaled; their
+  // events are resolved here: call after a sync point, e.g. once per fit)
+  double ms() {
+    double t_ms = 0.0;
+    for (auto& e : timing) {
+      float t = 0.f;
+      if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&t, e.first, e.second) == hipSuccess)
+        t_ms += 8.0 * t;
+      (void)hipEventDestroy(e.first);
+      (void)hipEventDestroy(e.second);
+    }
+    timing.clear();
+    return t_ms;
+  }
+
+  // (reduce-scatters, all-gathers, all-reduces, ms()) so far; the counters restart
+  std::vector<double> stats() {
+    std::vector<double> out{(double)calls[0], (double)calls[1], (double)calls[2], ms()};
+    calls[0] = calls[1] = calls[2] = 0;
+    return out;
+  }
+};
+
 struct ItemGroup {
   Tensor start, end, f0, meta, wave;
   int bt = 1;
@@ -263,7 +375,7 @@ class RfLevels {
       max_parts = mv + kSet * parity_;
       // data parallel: the max |g|, |h| slots all-reduced (MAX of the bit patterns of non-negative
       // doubles) before the quantisation reads them, so every rank quantises with one exponent
-      if (dp_) dp_all_reduce_max(maxv_.narrow(0, kSet * parity_, kSet), s);
+      if (dp_) comm_.all_reduce_max(maxv_.narrow(0, kSet * parity_, kSet), s);
       maxv = nullptr;
       parity_ ^= 1;
     }
@@ -312,15 +424,11 @@ class RfLevels {
 
   ~RfLevels() {
     if (g_ev_) (void)hipEventDestroy(g_ev_);
-    for (auto& e : dp_timing_) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
   }
   RfLevels(const RfLevels&) = delete;
   RfLevels& operator=(const RfLevels&) = delete;
 
-  // ---- GBDT trees of one process on the row-group engine: the whole level loop in here --------
+  // ---- GBDT trees on the row-group engine (one process or data parallel): the level loop in here
   // grower.device_tree_steps' generic loop spends ~33 us of interpreter time per level between the
   // plan's counts and the next level's first launch (profiles/r5/gbdt_host_profile_*.txt), which
   // the GPU sees as idle time at 1M rows. gbdt_root queues level 0 after the prologue; gbdt_levels
@@ -329,33 +437,18 @@ class RfLevels {
   // partition -- with the same kernels and arguments as the Python loop (trees bitwise equal:
   // tests/test_level_runner.py). Buffers are fixed: the level histograms alternate between two
   // tensors (each sized for its parity's widest level), the partition zeroing the next one.
+  //
+  // Under data parallelism (the dict carries the DP keys: "send", ...) it is the same level loop
+  // around the level's collectives (grower.device_tree_steps' shards branch, launch for launch):
+  // the row-group pass writes the built nodes' partial histograms straight into the shard-major
+  // send buffer, ONE reduce-scatter leaves this rank's feature shard of them in out[cur], the split
+  // search runs over the shard (the larger siblings subtracted inside it, rows from level_rows),
+  // ONE all-gather of the best-split tuples feeds the level plan (best over shards), then the
+  // partition zeroes the next level's send region on the way. The root totals ride in the root's
+  // reduce-scatter and the quantisation max is one all-reduce (inside prologue()): 13 collectives
+  // per depth-6 tree, issued through comm_ (DpComm); every other launch and the host waits are here.
+  // Sibling choice by rows is off: rows are rank-local, and every rank must build the same nodes.
   void gbdt_setup(const py::dict& c) {
-    rg_setup(c);
-    for (int k = 0; k < 2; ++k) {
-      g_hist_[k] = get(c, k ? "hist_b" : "hist_a");
-      int64_t need = 1;                     // (level d opens at most 2^d nodes)
-      for (int64_t d = k; d < max_depth_; d += 2) need = int64_t{1} << d;
-      FDX_CHECK(g_hist_[k].scalar_type() == at::kLong && g_hist_[k].dim() == 3 && g_hist_[k].size(2) == 2 &&
-                    g_hist_[k].is_contiguous() && g_hist_[k].size(0) >= need &&
-                    reinterpret_cast<uintptr_t>(g_hist_[k].data_ptr()) % 16 == 0,
-                "gbdt_setup: hist_a / hist_b [rows >= widest level of the parity, TB, 2] int64");
-    }
-    gh_.hist_stride = g_hist_[0].size(1);
-    FDX_CHECK(g_hist_[1].size(1) == gh_.hist_stride, "gbdt_setup: hist strides");
-    g_packed_ = get(c, "packed");
-    FDX_CHECK(g_packed_.scalar_type() == at::kLong && g_packed_.dim() == 2 && g_packed_.size(1) == 5 &&
-                  g_packed_.is_contiguous() && g_packed_.size(0) >= (int64_t{1} << (max_depth_ - 1)),
-              "gbdt_setup: packed [widest level, 5] int64");
-    // fewest-rows builds (LevelChooseArgs) where the row lists are counted by their own pass; the
-    // partition counts the rows in one grid pass (8 rows a thread, <= 8192 blocks)
-    const int64_t N = row_node_.numel();
-    g_choose_ = c["choose_rows"].cast<bool>() && (N + 7) / 8 <= 8192ll * 256;
-    if (g_choose_ && !g_rows_.defined()) g_rows_ = at::zeros({32 * 64}, row_node_.options());
-  }
-
-  // The row-group tables and fixed level buffers shared by the single-process (gbdt_setup) and
-  // the data-parallel (gbdt_dp_setup) GBDT level loops.
-  void rg_setup(const py::dict& c) {
     const Tensor ptr = get(c, "rg_ptr"), ent = get(c, "rg_ent"), gbase = get(c, "rg_gbase"),
                  gbin = get(c, "rg_gbin"), gmode = get(c, "rg_gmode"), wg = get(c, "rg_wg");
     const int64_t G = ptr.size(0), N = ptr.size(1) - 1;
@@ -438,62 +531,36 @@ class RfLevels {
     // where the partition does not write the row lists' per-slot counts (above 4M rows: 2048-row
     // list waves), it keeps its rows per next-level node per 512-row chunk (PartitionArgs
     // node_counts) and the lists skip their counting pass over row_node
-    const bool nc = !g_counted_ok_ && (c.contains("node_counts") ? c["node_counts"].cast<bool>() : true) &&
-                    fdx::rg_list_rows(N) % fdx::kPartWaveRows == 0;
+    const bool nc = !g_counted_ok_ && fdx::rg_list_rows(N) % fdx::kPartWaveRows == 0;
     g_node_counts_ = nc ? at::empty({64 * ((N + fdx::kPartWaveRows - 1) / fdx::kPartWaveRows)}, row_node_.options())
                         : Tensor();
     nc_base_ = nullptr;
-    g_part_multi_ = c["part_multi"].cast<bool>();
     FDX_CHECK(sub_of_.has_value() && counts_host_dev_ != nullptr, "gbdt_setup: sub_of and mapped counts");
     if (!g_ev_) FDX_CHECK(hipEventCreateWithFlags(&g_ev_, hipEventDisableTiming) == hipSuccess, "event");
-  }
-
-  // Level 0 of a tree whose prologue just ran (its root histogram: hist_a row 0, zeroed there).
-  void gbdt_root(int64_t tree) {
-    FDX_CHECK(g_ev_ != nullptr, "gbdt_root before gbdt_setup");
-    c10::hip::HIPGuard guard(dev_.index());
-    const hipStream_t s = cur_stream(dev_);
-    gbdt_level(0, 1, 1, tree, s);
-  }
-
-  // Levels 1 .. max_depth - 1; returns (n_open, n_build) of every level run, the root's first.
-  std::vector<int64_t> gbdt_levels(int64_t tree) {
-    c10::hip::HIPGuard guard(dev_.index());
-    const hipStream_t s = cur_stream(dev_);
-    std::vector<int64_t> shape{1, 1};
-    const Tensor& ch = st_["counts_host"];
-    const int64_t cw = ch.size(1);
-    for (int64_t d = 1; d < max_depth_; ++d) {
-      wait_event(g_ev_);
-      const volatile int32_t* row = p<int32_t>(ch) + (d - 1) * cw;     // (written by the plan itself)
-      const int32_t n_open = row[1], n_build = row[2];
-      if (n_open == 0) break;
-      FDX_CHECK(n_open <= g_hist_[d & 1].size(0) && n_build >= 1 && n_build <= fdx::kRgMaxSlots && n_build <= n_open,
-                "level counts");
-      gbdt_level(d, n_open, n_build, tree, s);
-      shape.push_back(n_open);
-      shape.push_back(n_build);
+    dp_ = c.contains("send");
+    // fewest-rows builds (LevelChooseArgs) where the row lists are counted by their own pass; the
+    // partition counts the rows in one grid pass (8 rows a thread, <= 8192 blocks)
+    g_choose_ = !dp_ && c["choose_rows"].cast<bool>() && (N + 7) / 8 <= 8192ll * 256;
+    if (g_choose_ && !g_rows_.defined()) g_rows_ = at::zeros({32 * 64}, row_node_.options());
+    if (!dp_) {
+      for (int k = 0; k < 2; ++k) {
+        g_hist_[k] = get(c, k ? "hist_b" : "hist_a");
+        int64_t need = 1;                     // (level d opens at most 2^d nodes)
+        for (int64_t d = k; d < max_depth_; d += 2) need = int64_t{1} << d;
+        FDX_CHECK(g_hist_[k].scalar_type() == at::kLong && g_hist_[k].dim() == 3 && g_hist_[k].size(2) == 2 &&
+                      g_hist_[k].is_contiguous() && g_hist_[k].size(0) >= need &&
+                      reinterpret_cast<uintptr_t>(g_hist_[k].data_ptr()) % 16 == 0,
+                  "gbdt_setup: hist_a / hist_b [rows >= widest level of the parity, TB, 2] int64");
+      }
+      a.hist_stride = g_hist_[0].size(1);
+      FDX_CHECK(g_hist_[1].size(1) == a.hist_stride, "gbdt_setup: hist strides");
+      g_packed_ = get(c, "packed");
+      FDX_CHECK(g_packed_.scalar_type() == at::kLong && g_packed_.dim() == 2 && g_packed_.size(1) == 5 &&
+                    g_packed_.is_contiguous() && g_packed_.size(0) >= (int64_t{1} << (max_depth_ - 1)),
+                "gbdt_setup: packed [widest level, 5] int64");
+      return;
     }
-    return shape;
-  }
-
-  // ---- GBDT trees under data parallelism: the same level loop around the level's collectives ----
-  // A DP level (grower.device_tree_steps' shards branch, launch for launch): the row-group pass
-  // writes the built nodes' partial histograms straight into the shard-major send buffer, ONE
-  // reduce-scatter (callback rs) leaves this rank's feature shard of them in out[cur], the split
-  // search runs over the shard (the larger siblings subtracted inside it, rows from level_rows),
-  // ONE all-gather (callback ag) of the best-split tuples feeds the level plan (best over shards),
-  // then the partition zeroes the next level's send region on the way. The root totals ride in the
-  // root's reduce-scatter (dp_root phase 0 / 1) and the quantisation max is one all-reduce (callback
-  // mx, inside prologue()): 13 collectives per depth-6 tree. The callbacks are Python (the process
-  // group's collectives on the current stream); every other launch and the host waits are here.
-  // Sibling choice by rows is off: rows are rank-local, and every rank must build the same nodes.
-  void gbdt_dp_setup(const py::dict& c) {
-    rg_setup(c);
-    dp_ = true;
-    dp_rs_cb_ = c["rs"];
-    dp_ag_cb_ = c["ag"];
-    dp_max_cb_ = c["mx"];
+    comm_.setup(c);
     dp_S_ = c["S"].cast<int64_t>();
     dp_Bs_ = c["Bs"].cast<int64_t>();
     dp_bin_lo_ = get(c, "bin_lo");
@@ -513,79 +580,65 @@ class RfLevels {
     dp_par_row_ = get(c, "par_row");
     dp_sib_row_ = get(c, "sib_row");
     dp_iota_ = get(c, "iota");
-    dp_direct_ = c.contains("comm") && !c["comm"].is_none() &&
-                 rccl_.load(c["rccl_lib"].cast<std::string>(), c["comm"].cast<int64_t>());
     const int64_t widest = int64_t{1} << std::max<int64_t>(max_depth_ - 1, 1);
     FDX_CHECK(dp_S_ >= 1 && dp_Bs_ >= 1 && dp_bin_lo_.numel() == dp_S_ + 1 && dp_bin_lo_.scalar_type() == at::kLong,
-              "gbdt_dp_setup: S, Bs, bin_lo [S + 1]");
+              "gbdt_setup: S, Bs, bin_lo [S + 1]");
     FDX_CHECK(dp_send_.scalar_type() == at::kLong && dp_send_.is_contiguous() &&
                   dp_send_.numel() >= dp_S_ * std::max<int64_t>(widest, 2) * dp_Bs_ * 2 &&
                   reinterpret_cast<uintptr_t>(dp_send_.data_ptr()) % 16 == 0,
-              "gbdt_dp_setup: send [S * max(2, widest level) * Bs * 2] int64");
+              "gbdt_setup: send [S * max(2, widest level) * Bs * 2] int64");
     for (int k = 0; k < 2; ++k)
       FDX_CHECK(dp_out_[k].scalar_type() == at::kLong && dp_out_[k].dim() == 3 && dp_out_[k].size(1) == dp_Bs_ &&
                     dp_out_[k].size(2) == 2 && dp_out_[k].is_contiguous() && dp_out_[k].size(0) >= std::max<int64_t>(widest, 2) &&
                     dp_row_of_[k].numel() >= widest,
-                "gbdt_dp_setup: out [max(2, widest level), Bs, 2], row_of");
+                "gbdt_setup: out [max(2, widest level), Bs, 2], row_of");
     FDX_CHECK(dp_ag_in_.scalar_type() == at::kLong && dp_ag_in_.dim() == 2 && dp_ag_in_.size(1) == 5 &&
                   dp_ag_in_.size(0) >= widest && dp_iota_.numel() >= fdx::kRgMaxSlots &&
                   dp_boff_.numel() == dp_nbins_.numel() + 1,
-              "gbdt_dp_setup: ag_in [widest, 5], iota, shard tables");
-    if (dp_direct_) dp_allt_buf_ = at::empty({dp_S_ * widest * 5}, dp_ag_in_.options());
+              "gbdt_setup: ag_in [widest, 5], iota, shard tables");
+    if (comm_.direct) dp_allt_buf_ = at::empty({dp_S_ * widest * 5}, dp_ag_in_.options());
   }
 
-  // The direct-RCCL collectives issued so far (reduce-scatter, all-gather, all-reduce) and the
-  // milliseconds of the timed ones (every 8th, scaled; events resolved here: call after a sync
-  // point, e.g. once per fit); the counters restart.
-  std::vector<double> dp_coll_stats() {
-    double ms = 0.0;
-    for (auto& e : dp_timing_) {
-      float t = 0.f;
-      if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&t, e.first, e.second) == hipSuccess)
-        ms += 8.0 * t;
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    dp_timing_.clear();
-    std::vector<double> out{(double)dp_calls_[0], (double)dp_calls_[1], (double)dp_calls_[2], ms};
-    dp_calls_[0] = dp_calls_[1] = dp_calls_[2] = 0;
-    return out;
-  }
-
-  bool dp_direct() const { return dp_direct_; }
-
-  // Prologue (with its max all-reduce) done by the caller; level 0 of a DP tree.
-  void gbdt_dp_root(int64_t tree) {
-    FDX_CHECK(dp_ && g_ev_ != nullptr, "gbdt_dp_root before gbdt_dp_setup");
+  // Level 0 of a tree whose prologue just ran (its root histogram: hist_a row 0, or under data
+  // parallelism the root's send region, zeroed there; the prologue did the max all-reduce).
+  void gbdt_root(int64_t tree) {
+    FDX_CHECK(g_ev_ != nullptr, "gbdt_root before gbdt_setup");
     c10::hip::HIPGuard guard(dev_.index());
-    gbdt_dp_level(0, 1, 1, tree, cur_stream(dev_));
+    gbdt_level(0, 1, 1, tree, cur_stream(dev_));
   }
 
-  // Levels 1 .. max_depth - 1 of a DP tree (host waits with the GIL released; the collective
-  // callbacks take it back); returns (n_open, n_build) of every level, the root's first.
-  std::vector<int64_t> gbdt_dp_levels(int64_t tree) {
+  // Levels 1 .. max_depth - 1 (called with the GIL released; the collective callbacks of a data-
+  // parallel level take it back); returns (n_open, n_build) of every level run, the root's first.
+  std::vector<int64_t> gbdt_levels(int64_t tree) {
     c10::hip::HIPGuard guard(dev_.index());
     const hipStream_t s = cur_stream(dev_);
     std::vector<int64_t> shape{1, 1};
     const Tensor& ch = st_["counts_host"];
     const int64_t cw = ch.size(1);
     for (int64_t d = 1; d < max_depth_; ++d) {
-      {
-        py::gil_scoped_release nogil;
-        wait_event(g_ev_);
-      }
-      const volatile int32_t* row = p<int32_t>(ch) + (d - 1) * cw;
+      wait_event(g_ev_);
+      const volatile int32_t* row = p<int32_t>(ch) + (d - 1) * cw;     // (written by the plan itself)
       const int32_t n_open = row[1], n_build = row[2];
       if (n_open == 0) break;
-      FDX_CHECK(n_open <= dp_ag_in_.size(0) && n_build >= 1 && n_build <= fdx::kRgMaxSlots && n_build <= n_open,
-                "dp level counts");
-      gbdt_dp_level(d, n_open, n_build, tree, s);
+      FDX_CHECK(n_open <= (dp_ ? dp_ag_in_.size(0) : g_hist_[d & 1].size(0)) && n_build >= 1 &&
+                    n_build <= fdx::kRgMaxSlots && n_build <= n_open, "level counts");
+      gbdt_level(d, n_open, n_build, tree, s);
       shape.push_back(n_open);
       shape.push_back(n_build);
     }
     dp_allt_ = Tensor();
     return shape;
   }
+
+  // The runner's direct-RCCL collectives so far (reduce-scatter, all-gather, all-reduce; the
+  // callbacks count their own) and the milliseconds of the timed ones (DpComm::stats: a sync point)
+  std::vector<double> dp_coll_stats() {
+    std::vector<double> st = comm_.stats();
+    if (!comm_.direct) st[0] = st[1] = st[2] = 0.0;
+    return st;
+  }
+
+  bool dp_direct() const { return comm_.direct; }
 
   // GBDT leaf update from the node table (leaf_values + leaf_update in one launch)
   void leaf_update(const Tensor& margin, double eta, double lambda, double mds) {
@@ -1062,14 +1115,30 @@ class RfLevels {
     return ct;
   }
 
-  // One GBDT level (the generic loop's rg branch + split_plan + partition, launch for launch).
+  // One GBDT level (the generic loop's rg branch, launch for launch): row lists + row-group pass,
+  // split search + level plan (one process: fused, split_plan; data parallel: around the level's
+  // reduce-scatter and all-gather), partition.
   void gbdt_level(int64_t d, int32_t n_open, int32_t n_build, int64_t tree, hipStream_t s) {
     const int cur = (int)(d & 1), nxt = cur ^ 1;
     const bool more = d + 1 < max_depth_;
-    const Tensor& hist = g_hist_[cur];
     fdx::RgHistArgs a = gh_;
-    a.hist = p<int64_t>(hist);
     a.nslots = n_build;
+    // the built nodes' histograms: the level's tensor, or (data parallel) their partials shard-major
+    // in the send buffer (slot k -> row k of every shard chunk; the root: + the totals row)
+    const int64_t R = n_build + (d == 0 ? 1 : 0);
+    Tensor send;
+    if (dp_) {
+      const int64_t subs = d == 0 ? 0 : n_build, chunk = R * dp_Bs_;
+      FDX_CHECK(R + subs <= dp_out_[cur].size(0) && dp_S_ * chunk * 2 <= dp_send_.numel(), "dp level rows");
+      send = dp_send_.narrow(0, 0, dp_S_ * chunk * 2).view({dp_S_, R, dp_Bs_, 2});
+      a.hist = p<int64_t>(send);
+      a.hist_stride = dp_Bs_;
+      a.nshards = (int32_t)dp_S_;
+      a.shard_lo = p<int64_t>(dp_bin_lo_);
+      a.shard_stride = chunk;
+    } else {
+      a.hist = p<int64_t>(g_hist_[cur]);
+    }
     if (d == 0) {
       a.slot_node = p<int32_t>(g_zero1_);
     } else {
@@ -1089,7 +1158,7 @@ class RfLevels {
       a.list = l.list;
       a.slot_start = l.slot_start;
       a.listdig = l.listdig;
-      a.slot_node = p<int32_t>(st_["s2n"]);
+      a.slot_node = p<int32_t>(dp_ ? dp_iota_ : st_["s2n"]);
       a.wg_g = g_wl_.g;
       a.wg_p = g_wl_.p;
       a.wg_np = g_wl_.np;
@@ -1099,26 +1168,78 @@ class RfLevels {
         a.em_min_rows = g_em_min_rows_;
       }
     }
-    if (g_part_ && (n_build == 1 || g_part_multi_)) {
+    if (g_part_) {
       a.part = p<int64_t>(*g_part_);
       a.wg_first = p<int32_t>(d == 0 ? *g_wg_first_ : *g_wg_first_list_);
+    }
+    if (dp_ && d == 0) {          // (+ the local root sums into the totals row of every shard chunk)
+      FDX_CHECK(root_pending_ != nullptr, "dp root level without its prologue");
+      a.root_parts = root_pending_;
+      root_pending_ = nullptr;
     }
     fdx::launch_rg_hist(a, s);
     C10_HIP_KERNEL_LAUNCH_CHECK();
     const Tensor n_open_ptr = d == 0 ? g_one_ : st_["counts"].select(0, d - 1).narrow(0, 1, 1);
-    const optional<Tensor> prev = d == 0 ? optional<Tensor>() : optional<Tensor>(g_hist_[nxt]);
-    split_plan(d, n_open, hist.narrow(0, 0, n_open),
-               d == 0 ? st_["stats"].narrow(0, 0, 1) : g_totals_[cur].narrow(0, 0, n_open), g_boff_, c10::nullopt,
-               tree, g_packed_.narrow(0, 0, n_open), g_wide_, g_open_[cur].narrow(0, 0, n_open), n_open_ptr,
-               g_open_[nxt], g_totals_[nxt], false, c10::nullopt, c10::nullopt, {}, prev);
+    const Tensor open = g_open_[cur].narrow(0, 0, n_open);
+    if (!dp_) {
+      const optional<Tensor> prev = d == 0 ? optional<Tensor>() : optional<Tensor>(g_hist_[nxt]);
+      split_plan(d, n_open, g_hist_[cur].narrow(0, 0, n_open),
+                 d == 0 ? st_["stats"].narrow(0, 0, 1) : g_totals_[cur].narrow(0, 0, n_open), g_boff_, c10::nullopt,
+                 tree, g_packed_.narrow(0, 0, n_open), g_wide_, open, n_open_ptr, g_open_[nxt], g_totals_[nxt], false,
+                 c10::nullopt, c10::nullopt, {}, prev);
+    } else {
+      const Tensor& out = dp_out_[cur];
+      comm_.reduce_scatter(send, out.narrow(0, 0, R), s);
+      if (d > 0) {
+        // the built rows stay where the collective wrote them, the larger siblings behind them (rows
+        // written by the previous level's plan: LevelPlanArgs lr_*), subtracted inside the search
+        find_prev_ = p<int64_t>(dp_out_[nxt]);
+        find_sub_par_ = p<int32_t>(dp_par_row_);
+        find_sub_sib_ = p<int32_t>(dp_sib_row_);
+      }
+      // split search over this rank's features (+ the fused subtraction), best tuples into ag_in
+      Tensor ag_in = dp_ag_in_.narrow(0, 0, n_open);
+      // (the root's totals: the reduced totals row)
+      const Tensor totals = d == 0 ? out.select(0, R - 1).narrow(0, 0, 1) : g_totals_[cur].narrow(0, 0, n_open);
+      const bool any = find(out, totals, dp_boff_, dp_nbins_, dp_zbin_, dp_fid_, open, c10::nullopt, tree, ag_in,
+                            d > 0 ? optional<Tensor>(dp_row_of_[cur]) : c10::nullopt, dp_wide_, s);
+      find_prev_ = nullptr;
+      find_sub_par_ = find_sub_sib_ = nullptr;
+      if (any)
+        fdx::launch_split_best(p<double>(gain_), p<int32_t>(sbin_), p<int64_t>(sleft_), n_open,
+                               (int32_t)dp_nbins_.numel(), dp_f0_, p<int64_t>(ag_in), s, &last_split_);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+      // [S, n_open, 5] (direct: into the runner's buffer; else the callback's own result)
+      dp_allt_ = comm_.all_gather(ag_in, comm_.direct ? dp_allt_buf_.narrow(0, 0, dp_S_ * ag_in.numel())
+                                                            .view({dp_S_, ag_in.size(0), ag_in.size(1)}) : Tensor(), s);
+      FDX_CHECK(dp_allt_.dim() == 3 && dp_allt_.size(0) == dp_S_ && dp_allt_.size(1) == n_open &&
+                    dp_allt_.is_contiguous(), "all-gathered best splits [S, n_open, 5]");
+      fdx::LevelPlanArgs pa = plan_args(d, n_open, dp_allt_, open, n_open_ptr, g_open_[nxt], g_totals_[nxt]);
+      if (d == 0) pa.root_tot = p<int64_t>(totals);
+      if (more) {                   // the next level's histogram rows
+        pa.lr_prev = d > 0 ? p<int32_t>(dp_row_of_[cur]) : nullptr;
+        pa.lr_row_of = p<int32_t>(dp_row_of_[nxt]);
+        pa.lr_dst = p<int32_t>(dp_dst_row_);
+        pa.lr_par = p<int32_t>(dp_par_row_);
+        pa.lr_sib = p<int32_t>(dp_sib_row_);
+      }
+      const bool zc = counts_zero_copy(pa, d, false, {});
+      fdx::launch_level_plan(pa, s);
+      after_plan(d, n_open, g_open_[nxt], tree, false, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt,
+                 c10::nullopt, c10::nullopt, c10::nullopt, 0, {}, s, zc);
+    }
     FDX_CHECK(hipEventRecord(g_ev_, s) == hipSuccess, "level event record");
+    // zeroed by the partition on the way: the next level's histograms, or (data parallel) its send
+    // region (its builds <= this level's open nodes)
     optional<Tensor> zero;
-    if (more) {
+    if (more && dp_) {
+      zero = dp_send_.narrow(0, 0, dp_S_ * n_open * dp_Bs_ * 2);
+    } else if (more) {
       FDX_CHECK(2 * (int64_t)n_open <= g_hist_[nxt].size(0), "next level rows");
       zero = g_hist_[nxt].narrow(0, 0, 2 * (int64_t)n_open);
     }
     g_counted_ = more && g_counted_ok_;
-    const bool choose = more && g_choose_ && !g_counted_;
+    const bool choose = more && g_choose_ && !g_counted_;      // (never under data parallelism)
     const Tensor& counts = st_["counts"];
     const int32_t* base = d == 0 ? p<int32_t>(g_one_) : p<int32_t>(counts) + (d - 1) * counts.size(1) + 3;
     // (per-node counts cover the next level's first 64 nodes: 2 n_open of them)
@@ -1145,155 +1266,6 @@ class RfLevels {
     }
   }
 
-  void gbdt_dp_level(int64_t d, int32_t n_open, int32_t n_build, int64_t tree, hipStream_t s) {
-    const int cur = (int)(d & 1), nxt = cur ^ 1;
-    const bool more = d + 1 < max_depth_;
-    const int64_t S = dp_S_, Bs = dp_Bs_;
-    const int64_t R = n_build + (d == 0 ? 1 : 0), subs = d == 0 ? 0 : n_build;   // (root: + the totals row)
-    const int64_t chunk = R * Bs;
-    FDX_CHECK(R + subs <= dp_out_[cur].size(0) && S * chunk * 2 <= dp_send_.numel(), "dp level rows");
-    Tensor send = dp_send_.narrow(0, 0, S * chunk * 2).view({S, R, Bs, 2});
-    const Tensor& out = dp_out_[cur];
-    // the built nodes' partial histograms, shard-major (slot k -> row k of every shard chunk)
-    fdx::RgHistArgs a = gh_;
-    a.hist = p<int64_t>(send);
-    a.hist_stride = Bs;
-    a.nslots = n_build;
-    a.nshards = (int32_t)S;
-    a.shard_lo = p<int64_t>(dp_bin_lo_);
-    a.shard_stride = chunk;
-    if (d == 0) {
-      a.slot_node = p<int32_t>(g_zero1_);
-    } else {
-      const bool em = n_build == 1 && g_emdig_.has_value();
-      fdx::RgListArgs l = gl_;
-      l.nslots = n_build;
-      l.wave_count = l.slot_count + 2 * n_build;
-      l.counted = g_counted_ ? 1 : 0;
-      l.masked = em ? reinterpret_cast<uint32_t*>(p<int32_t>(*g_emdig_)) : nullptr;
-      if (nc_base_ != nullptr) {                  // (the last partition's counts per node)
-        l.node_counts = p<int32_t>(g_node_counts_);
-        l.nc_base = nc_base_;
-      }
-      fdx::launch_rg_list(l, s);
-      a.list = l.list;
-      a.slot_start = l.slot_start;
-      a.listdig = l.listdig;
-      a.slot_node = p<int32_t>(dp_iota_);
-      a.wg_g = g_wl_.g;
-      a.wg_p = g_wl_.p;
-      a.wg_np = g_wl_.np;
-      a.n_wg = g_wl_.n;
-      if (a.erow && em) {
-        a.emdig = l.masked;
-        a.em_min_rows = g_em_min_rows_;
-      }
-    }
-    if (g_part_ && (n_build == 1 || g_part_multi_)) {
-      a.part = p<int64_t>(*g_part_);
-      a.wg_first = p<int32_t>(d == 0 ? *g_wg_first_ : *g_wg_first_list_);
-    }
-    if (d == 0) {                 // (+ the local root sums into the totals row of every shard chunk)
-      FDX_CHECK(root_pending_ != nullptr, "dp root level without its prologue");
-      a.root_parts = root_pending_;
-      root_pending_ = nullptr;
-    }
-    fdx::launch_rg_hist(a, s);
-    C10_HIP_KERNEL_LAUNCH_CHECK();
-    dp_reduce_scatter(send, out.narrow(0, 0, R), s);
-    if (d > 0) {
-      // the built rows stay where the collective wrote them, the larger siblings behind them (rows
-      // written by the previous level's plan: LevelPlanArgs lr_*), subtracted inside the search
-      find_prev_ = p<int64_t>(dp_out_[nxt]);
-      find_sub_par_ = p<int32_t>(dp_par_row_);
-      find_sub_sib_ = p<int32_t>(dp_sib_row_);
-    }
-    // split search over this rank's features (+ the fused subtraction), best tuples into ag_in
-    Tensor ag_in = dp_ag_in_.narrow(0, 0, n_open);
-    const Tensor open = g_open_[cur].narrow(0, 0, n_open);
-    // (the root's totals: the reduced totals row)
-    const Tensor totals = d == 0 ? out.select(0, R - 1).narrow(0, 0, 1) : g_totals_[cur].narrow(0, 0, n_open);
-    const bool any = find(out, totals, dp_boff_, dp_nbins_, dp_zbin_, dp_fid_, open, c10::nullopt, tree, ag_in,
-                          d > 0 ? optional<Tensor>(dp_row_of_[cur]) : c10::nullopt, dp_wide_, s);
-    find_prev_ = nullptr;
-    find_sub_par_ = find_sub_sib_ = nullptr;
-    if (any)
-      fdx::launch_split_best(p<double>(gain_), p<int32_t>(sbin_), p<int64_t>(sleft_), n_open,
-                             (int32_t)dp_nbins_.numel(), dp_f0_, p<int64_t>(ag_in), s, &last_split_);
-    C10_HIP_KERNEL_LAUNCH_CHECK();
-    dp_allt_ = dp_all_gather(ag_in, s);                  // [S, n_open, 5]
-    FDX_CHECK(dp_allt_.dim() == 3 && dp_allt_.size(0) == S && dp_allt_.size(1) == n_open && dp_allt_.is_contiguous(),
-              "all-gathered best splits [S, n_open, 5]");
-    const Tensor n_open_ptr = d == 0 ? g_one_ : st_["counts"].select(0, d - 1).narrow(0, 1, 1);
-    fdx::LevelPlanArgs pa = plan_args(d, n_open, dp_allt_, open, n_open_ptr, g_open_[nxt], g_totals_[nxt]);
-    if (d == 0) pa.root_tot = p<int64_t>(totals);
-    if (more) {                   // the next level's histogram rows
-      pa.lr_prev = d > 0 ? p<int32_t>(dp_row_of_[cur]) : nullptr;
-      pa.lr_row_of = p<int32_t>(dp_row_of_[nxt]);
-      pa.lr_dst = p<int32_t>(dp_dst_row_);
-      pa.lr_par = p<int32_t>(dp_par_row_);
-      pa.lr_sib = p<int32_t>(dp_sib_row_);
-    }
-    const bool zc = counts_zero_copy(pa, d, false, {});
-    fdx::launch_level_plan(pa, s);
-    after_plan(d, n_open, g_open_[nxt], tree, false, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt,
-               c10::nullopt, c10::nullopt, c10::nullopt, 0, {}, s, zc);
-    FDX_CHECK(hipEventRecord(g_ev_, s) == hipSuccess, "level event record");
-    // the partition zeroes the next level's send region (its builds <= this level's open nodes)
-    optional<Tensor> zero;
-    if (more) zero = dp_send_.narrow(0, 0, S * n_open * Bs * 2);
-    g_counted_ = more && g_counted_ok_;
-    const bool nc = more && !g_counted_ && g_node_counts_.defined() && 2 * (int64_t)n_open <= 64;
-    const int32_t* base = d == 0 ? p<int32_t>(g_one_) : p<int32_t>(st_["counts"]) + (d - 1) * st_["counts"].size(1) + 3;
-    rows_base_ = nc ? base : nullptr;
-    partition(d, n_open, false, zero, false, g_counted_ ? optional<Tensor>(g_list_work_) : c10::nullopt);
-    rows_base_ = nullptr;
-    nc_base_ = nc ? base : nullptr;
-  }
-
-  // timing events around every 8th direct collective (dp_coll_stats)
-  struct CollTimer {
-    RfLevels* r;
-    hipStream_t s;
-    hipEvent_t b = nullptr;
-    CollTimer(RfLevels* r_, hipStream_t s_, int kind) : r(r_), s(s_) {
-      ++r->dp_calls_[kind];
-      if ((r->dp_timed_++ & 7) == 0 && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(b, s);
-    }
-    ~CollTimer() {
-      hipEvent_t e = nullptr;
-      if (b && hipEventCreate(&e) == hipSuccess && hipEventRecord(e, s) == hipSuccess) r->dp_timing_.emplace_back(b, e);
-    }
-  };
-
-  void dp_reduce_scatter(const Tensor& send, const Tensor& out, hipStream_t s) {
-    if (!dp_direct_) {
-      dp_rs_cb_(send, out);
-      return;
-    }
-    CollTimer t(this, s, 0);
-    rccl_.check(rccl_.rs(send.data_ptr(), out.data_ptr(), (size_t)out.numel(), ncclInt64, ncclSum, rccl_.comm, s),
-                "ncclReduceScatter");
-  }
-
-  Tensor dp_all_gather(const Tensor& in, hipStream_t s) {
-    if (!dp_direct_) return dp_ag_cb_(in).cast<Tensor>();
-    CollTimer t(this, s, 1);
-    Tensor out = dp_allt_buf_.narrow(0, 0, dp_S_ * in.numel()).view({dp_S_, in.size(0), in.size(1)});
-    rccl_.check(rccl_.ag(in.data_ptr(), out.data_ptr(), (size_t)in.numel(), ncclInt64, rccl_.comm, s), "ncclAllGather");
-    return out;
-  }
-
-  void dp_all_reduce_max(const Tensor& buf, hipStream_t s) {
-    if (!dp_direct_) {
-      dp_max_cb_(buf);
-      return;
-    }
-    CollTimer t(this, s, 2);
-    rccl_.check(rccl_.ar(buf.data_ptr(), buf.data_ptr(), (size_t)buf.numel(), ncclInt64, ncclMax, rccl_.comm, s),
-                "ncclAllReduce");
-  }
-
   std::vector<ItemGroup> groups_;
   Tensor csc_row_, csc_bin_, colptr_, nbins_, zbin_, fid_orig_, rowdig_, row_node_, kexp_;
   optional<Tensor> h_row_, h_key_, rowpack_, dense_, hot_row_, node_dense_, wide_, dig16_, fmix_;
@@ -1310,18 +1282,14 @@ class RfLevels {
   const int32_t* find_sub_par_ = nullptr;
   const int32_t* find_sub_sib_ = nullptr;
   optional<Tensor> sub_of_;
-  // data-parallel GBDT level loop (gbdt_dp_setup)
+  // data-parallel GBDT levels (gbdt_setup with the DP keys)
   bool dp_ = false;
-  py::object dp_rs_cb_, dp_ag_cb_, dp_max_cb_;
+  DpComm comm_;
   int64_t dp_S_ = 1, dp_Bs_ = 1, dp_f0_ = 0;
   Tensor dp_bin_lo_, dp_send_, dp_out_[2], dp_row_of_[2], dp_ag_in_, dp_boff_, dp_nbins_, dp_zbin_, dp_fid_,
       dp_dst_row_, dp_par_row_, dp_sib_row_, dp_iota_, dp_allt_;
   optional<Tensor> dp_wide_;
-  bool dp_direct_ = false;
-  Rccl rccl_;
   Tensor dp_allt_buf_;
-  int64_t dp_calls_[3] = {0, 0, 0}, dp_timed_ = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> dp_timing_;
   bool build_all_ = true;
   int mode_ = 1, max_depth_ = 5, wps_ = 256;
   double min_gain_ = 0.0, lambda_ = 1.0, mcw_ = 1.0;
@@ -1340,7 +1308,7 @@ class RfLevels {
     int32_t n;
   } g_wl_{};                               // the listed levels' work table
   int64_t g_em_min_rows_ = 0;
-  bool g_counted_ok_ = false, g_counted_ = false, g_part_multi_ = false, g_choose_ = false;
+  bool g_counted_ok_ = false, g_counted_ = false, g_choose_ = false;
   Tensor g_rows_;
   const int32_t* rows_base_ = nullptr;
   bool rows_choose_ = false;                     // (partition(): rows_out for LevelChooseArgs)
@@ -1425,10 +1393,7 @@ class RfBatch {
       f0_ = c["f0"].cast<int64_t>();
       Fa_s_ = c["Fa_s"].cast<int64_t>();
       max_shard_features_ = c["max_shard_features"].cast<int64_t>();
-      rs_cb_ = c["rs"];
-      ag_cb_ = c["ag"];
-      direct_ = c.contains("comm") && !c["comm"].is_none() &&
-                rccl_.load(c["rccl_lib"].cast<std::string>(), c["comm"].cast<int64_t>());
+      comm_.setup(c);
     }
     const auto dev = lanes_[0].r->dev_;
     host_ = at::empty({kRegions * kRegion}, at::TensorOptions().dtype(at::kByte).pinned_memory(true));
@@ -1443,10 +1408,6 @@ class RfBatch {
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ev_, done_})
       if (e) (void)hipEventDestroy(e);
-    for (auto& e : timing_) {
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
     for (auto& ln : lanes_) ln.r->rec_ = nullptr;
   }
   RfBatch(const RfBatch&) = delete;
@@ -1541,9 +1502,9 @@ class RfBatch {
     flush(s);
     live_.clear();
     FDX_CHECK(hipEventRecord(done_, s) == hipSuccess, "event");
-    stat_[5] = rs_calls_;
-    stat_[6] = ag_calls_;
-    rs_calls_ = ag_calls_ = 0;
+    stat_[5] = comm_.calls[0];       // (every call, direct or callback; the timing events stay pending)
+    stat_[6] = comm_.calls[1];
+    comm_.calls[0] = comm_.calls[1] = 0;
     return stat_;
   }
 
@@ -1558,7 +1519,7 @@ class RfBatch {
     return finish(parity);
   }
 
-  bool direct() const { return direct_; }
+  bool direct() const { return comm_.direct; }
 
   // host seconds since the last call: queuing the levels (recording + flushes), of which the
   // flushes (argument packing, copies, launches), and the waits for level counts
@@ -1568,20 +1529,8 @@ class RfBatch {
     return out;
   }
 
-  // Milliseconds of the direct collectives since the last call (every 8th timed, scaled; waits for
-  // their events)
-  double coll_ms() {
-    double ms = 0.0;
-    for (auto& e : timing_) {
-      float t = 0.f;
-      if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&t, e.first, e.second) == hipSuccess)
-        ms += 8.0 * t;
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    timing_.clear();
-    return ms;
-  }
+  // Milliseconds of the direct collectives since the last call (DpComm::ms: waits for their events)
+  double coll_ms() { return comm_.ms(); }
 
   // The last grow's node tables are in the lanes' arena_host (GIL released while waiting).
   void wait() {
@@ -1808,9 +1757,9 @@ class RfBatch {
     pack(s);
     launch(0, m_hist, s);
     if (dp_) {
-      reduce_scatter(send, out, s);
+      comm_.reduce_scatter(send, out, s);
       launch(m_hist, m_split, s);
-      all_gather(ag_in, allt, s);
+      comm_.all_gather(ag_in, allt, s);      // (the recorded plans read allt: a callback's result is copied in)
     }
     launch(m_split, m_plan, s);
     FDX_CHECK(hipEventRecord(ev_, s) == hipSuccess, "level event");
@@ -1832,44 +1781,6 @@ class RfBatch {
   Tensor buffer(Tensor& b, int64_t n) {
     if (!b.defined() || b.numel() < n) b = at::empty({std::max<int64_t>(n, 1)}, i64_);
     return b.narrow(0, 0, n);
-  }
-
-  // timing events around every 8th direct collective (coll_ms)
-  struct Timed {
-    RfBatch* b;
-    hipStream_t s;
-    hipEvent_t e0 = nullptr;
-    Timed(RfBatch* b_, hipStream_t s_) : b(b_), s(s_) {
-      if ((b->timed_++ & 7) == 0 && hipEventCreate(&e0) == hipSuccess) (void)hipEventRecord(e0, s);
-    }
-    ~Timed() {
-      hipEvent_t e1 = nullptr;
-      if (e0 && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e1, s) == hipSuccess) b->timing_.emplace_back(e0, e1);
-    }
-  };
-
-  void reduce_scatter(const Tensor& send, const Tensor& out, hipStream_t s) {
-    ++rs_calls_;
-    if (!direct_) {
-      rs_cb_(send, out);
-      return;
-    }
-    Timed t(this, s);
-    rccl_.check(rccl_.rs(send.data_ptr(), out.data_ptr(), (size_t)out.numel(), ncclInt64, ncclSum, rccl_.comm, s),
-                "ncclReduceScatter");
-  }
-
-  // in [n, 5] from every rank into out [S, n, 5] (the callback's result is copied there on the stream)
-  void all_gather(const Tensor& in, const Tensor& out, hipStream_t s) {
-    ++ag_calls_;
-    if (!direct_) {
-      const Tensor r = ag_cb_(in).cast<Tensor>();
-      FDX_CHECK(r.numel() == out.numel(), "all-gather callback result size");
-      out.copy_(r.view_as(out));
-      return;
-    }
-    Timed t(this, s);
-    rccl_.check(rccl_.ag(in.data_ptr(), out.data_ptr(), (size_t)in.numel(), ncclInt64, rccl_.comm, s), "ncclAllGather");
   }
 
   // Issues what the live lanes recorded: position i of every lane's record is one lane-batched
@@ -2024,17 +1935,14 @@ class RfBatch {
   int64_t D_ = 5, listed_max_ = 2, d_ = 0, n_trees_ = 0;
   double host_s_[3] = {0.0, 0.0, 0.0};
   std::vector<int64_t> stat_;
-  bool presel_ = true, dp_ = false, compact_ = false, direct_ = false;
+  bool presel_ = true, dp_ = false, compact_ = false;
   Tensor boff_, one_, zero1_, iota_;
   optional<Tensor> wide_;
   // data parallel
   int64_t S_ = 1, Bs_full_ = 1, max_nb_ = 1, f0_ = 0, Fa_s_ = 0, max_shard_features_ = 0;
   Tensor shard_of_, sh_local_full_, sh_boff_, sh_nbins_, sh_zbin_, sh_fid_, sh_fs_, nbins_all_;
-  py::object rs_cb_, ag_cb_;
-  Rccl rccl_;
+  DpComm comm_;
   Tensor send_, out_, ag_in_, allt_;
-  int64_t rs_calls_ = 0, ag_calls_ = 0, timed_ = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_;
   // argument staging (pinned host + device, two halves by level parity)
   Tensor host_, dev_args_;
   int half_ = -1;
@@ -2064,13 +1972,10 @@ void register_level_ops(pybind11::module& m) {
       .def("leaf_update", &RfLevels::leaf_update)
       .def("gbdt_setup", &RfLevels::gbdt_setup)
       .def("gbdt_root", &RfLevels::gbdt_root)
-      .def("gbdt_dp_setup", &RfLevels::gbdt_dp_setup)
-      .def("gbdt_dp_root", &RfLevels::gbdt_dp_root)
-      .def("gbdt_dp_levels", &RfLevels::gbdt_dp_levels)
       .def("dp_coll_stats", &RfLevels::dp_coll_stats)
       .def("dp_direct", &RfLevels::dp_direct)
-      // (no Python objects inside: the GIL is released for the level loop and its host waits, so a
-      // concurrent forest thread keeps running)
+      // (the GIL is released for the level loop and its host waits, so a concurrent forest thread
+      // keeps running; the only Python inside, DpComm's callbacks, takes it back)
       .def("gbdt_levels", &RfLevels::gbdt_levels, py::call_guard<py::gil_scoped_release>());
   py::class_<RfBatch>(m, "RfBatch")
       .def(py::init<const py::dict&>())

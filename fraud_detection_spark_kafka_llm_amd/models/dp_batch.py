@@ -376,8 +376,8 @@ def drive(steps, batcher: Optional[LevelBatcher] = None):
 
 
 class _DpCollectives:
-    """The level collectives the runner's data-parallel GBDT loop calls back into
-    (csrc/bindings_level.cpp gbdt_dp_level): the level's reduce-scatter into the runner's buffer,
+    """The level collectives the runners' data-parallel levels call back into
+    (csrc/bindings_level.cpp DpComm): the level's reduce-scatter into the runner's buffer,
     the all-gather of the best-split tuples, the quantisation max (in place)."""
 
     def __init__(self, coll, dev: torch.device):

@@ -91,7 +91,7 @@ class ForestLanes:
 def batch_ok(Q: Quantized, params: GrowParams, weight) -> bool:
     """The lockstep batch covers the default sampled-RF configuration on the device (the lean
     runner level loop with fused packed row state and the LDS-atomic count passes)."""
-    return (BATCH and Q.device.type == "cuda" and G.NATIVE_LEVELS and G.SAMPLED and G.FUSED_PACK and
+    return (BATCH and Q.device.type == "cuda" and G.NATIVE_LEVELS and G.FUSED_PACK and
             G.RF_LDS and params.feat_k > 0 and G._choose_np(params, weight) == 1 and params.max_depth >= 1 and
             G.device_levels_ok(params, weight))
 
@@ -103,9 +103,8 @@ class ForestBatch:
 
     def __init__(self, Q: Quantized, wss: list, params: GrowParams, coll=None, shards: list = None):
         dev = Q.device
-        presel = G.PRESELECT and Q.n_rows >= G.PRESELECT_MIN_ROWS
         item_groups = Q.groups + Q.hot_groups
-        sel_ids = [gi for gi, grp in enumerate(item_groups) if grp.num_items] if presel else []
+        sel_ids = [gi for gi, grp in enumerate(item_groups) if grp.num_items] if G.PRESELECT else []
         dp = shards is not None and shards[0] is not None
         compact = dp and 0 < params.feat_k < Q.num_features and \
             (G.RF_COMPACT == "1" or (G.RF_COMPACT == "auto" and shards[0].S > 1))
@@ -156,9 +155,9 @@ class ForestBatch:
                        sh_local=sh._local, sh_boff=sh.boff, sh_nbins=sh.nbins, sh_zbin=sh.zbin, sh_fid=sh.fid_orig,
                        sh_fs=sh._fs_dev, nbins_all=Q.nbins, f0=int(sh.f0), Fa_s=int(sh.Fa),
                        max_shard_features=int(sh.max_shard_features),
-                       wide=G._wide_features(sh.nbins, sh.Fa) if G.SPLIT_WIDE else None)
+                       wide=G._wide_features(sh.nbins, sh.Fa))
         else:
-            cfg["wide"] = G._wide_features(Q.nbins, Q.Fa) if G.SPLIT_WIDE else None
+            cfg["wide"] = G._wide_features(Q.nbins, Q.Fa)
         self.cfg = cfg
         self.native = None
 

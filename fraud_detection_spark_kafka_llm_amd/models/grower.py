@@ -16,8 +16,8 @@ nodes batched into every launch):
      active work items);
   5. partition of the rows to the children (zeroing the next level's histograms on the way).
 The host reads a 16-byte count row per level and the node table once per tree. Drivers, fastest
-first: the native runner's C++ level loops (csrc/bindings_level.cpp: RfLevels.gbdt_levels /
-gbdt_dp_levels for GBDT, RfBatch for RF trees in lockstep batches, models/forest_batch.py), the
+first: the native runner's C++ level loops (csrc/bindings_level.cpp: RfLevels.gbdt_levels for GBDT
+in one process and data parallel, RfBatch for RF trees in lockstep batches, models/forest_batch.py), the
 Python device loop ``device_tree_steps`` (the test oracle of the native loops, and the CPU path
 through the kernels' host twins), and the host loop ``grow_tree`` (deep trees). The data-parallel
 machinery (level counters, LevelBatcher, feature shards, the runners' collectives) is in
@@ -65,18 +65,17 @@ HIST_STREAMS = 4
 # histograms from the row-group CSR of the built rows, in place of the CSC / dense passes
 ROWHIST = True
 RG_DBG = 0   # diagnostics only (csrc/tree.h RgHistArgs::dbg)
-# RF passes over sampled features: packed row state (slot + class counts in one word per row) and
-# a device-compacted list of the active work items (tree_hist_sampled)
-SAMPLED = True
+# RF passes over sampled features (class counts, np = 1) read a packed row state (slot + class
+# counts in one word per row) and a device-compacted list of the active work items
+# (tree_hist_sampled); with at most this many open nodes the list is compacted by the pass itself
 LISTED_MAX_NODES = 2
 # RF levels >= 1 launch one wave per active work item from lists compacted with the previous
-# level's plan (0: the r4 passes, a wave per item slot or a fixed listed grid)
+# level's plan (0: the r4 passes, a wave per item slot or a fixed listed grid), on shards of any
+# size: once the packed items skip their unsampled features and the selects of a level are one
+# launch, the listed passes win at 1.25M rows too (DP=8 shard, forced collectives: 0.456 -> 0.446 s
+# a forest, profiles/r5/rf_lean_presel_ab_1M.jsonl; before, 143 -> 207 us a pass the other way); at
+# 10M rows they win (0.768 -> 0.747 s)
 PRESELECT = True
-# ... on shards of at least this many rows. Once the packed items skip their unsampled features
-# and the selects of a level are one launch, the listed passes win at 1.25M rows too (DP=8 shard,
-# forced collectives: 0.456 -> 0.446 s a forest, profiles/r5/rf_lean_presel_ab_1M.jsonl; before,
-# 143 -> 207 us a pass the other way); at 10M rows they win (0.768 -> 0.747 s)
-PRESELECT_MIN_ROWS = 0
 # RF levels >= 1 read the packed row state (slot | class-count digits) written by the previous
 # level's partition instead of a row pass of their own (slot pack / masked digits: ~87 us per level
 # at 10M rows, 173 ms of a 500-tree forest's kernel time, profiles/r5/NOTES.md)
@@ -84,29 +83,22 @@ FUSED_PACK = True
 # RF device levels issue their kernels through the native per-level runner (csrc/bindings_level.cpp
 # RfLevels: hist / split / plan / partition, one host call each) instead of ~20 Python-level calls
 NATIVE_LEVELS = True
-# single-process runner levels subtract the larger siblings inside the split search
-SPLIT_SUBTRACT = True
 # the partition's row pass writes the next level's row-list counts (runner levels, <= 4M rows)
 PARTITION_COUNTS = True
-# single-slot row-group passes reduce per-workgroup partial tables (0: every workgroup's atomics)
+# row-group passes reduce per-workgroup partial tables (0: every workgroup's atomics); in the
+# listed passes over several slots a workgroup whose chunk straddles a slot boundary still
+# flushes with atomics
 RG_PARTIALS = True
-# ... and so do the listed passes over several slots (a workgroup whose chunk straddles a slot
-# boundary still flushes with atomics)
-RG_PARTIALS_MULTI = True
-# single-process GBDT trees on the row-group engine: the level loop runs in the runner (C++,
-# RfLevels.gbdt_levels; 0: the generic Python loop)
+# GBDT trees on the row-group engine, one process or data parallel: the level loop runs in the
+# runner (C++, RfLevels.gbdt_levels; 0: the generic Python loop)
 GBDT_CXX_LEVELS = True
-# ... which builds the sibling with fewer rows (not the smaller hessian sum) where the row lists
-# count their own rows (above 4M rows, or FDX_PARTITION_COUNTS=0): same trees, shorter lists;
-# the partition's rows per node, kept per 512-row wave, also stand in for the lists' counting pass
+# ... which, in one process, builds the sibling with fewer rows (not the smaller hessian sum) where
+# the row lists count their own rows (above 4M rows, or PARTITION_COUNTS off): same trees, shorter
+# lists; the partition's rows per node, kept per 512-row wave, also stand in for the lists'
+# counting pass
 GBDT_CHOOSE_ROWS = True
-LIST_NODE_COUNTS = True
 # RF / DT count passes: the LDS-atomic kernel (one ds_add_u64 per entry) instead of i8 MFMA
 RF_LDS = True
-# split search: a wave per (node, feature) for the features with > 16 bins
-SPLIT_WIDE = True
-# partition splits on dense-block features in the row pass (FDX_PARTITION_DENSE=0: CSC column pass)
-PARTITION_DENSE = True
 # RF levels under data parallelism reduce-scatter only the bins of the level's sampled features
 # (FeatureShards.sample_compact). "auto": when the reduce-scatter crosses ranks (world > 1; at
 # world 1 it is a local copy and the layout pass only costs); "1" always (the world-1 RCCL
@@ -387,14 +379,7 @@ def _best_splits(C, hist, totals, boff, nbins, zbin, fid_orig, node_ids, kexp, p
     out_gain, out_bin, out_left = bufs
     # features with > 16 bins get a wave each (tree_kernels.hip split_wide_kernel): listed once per
     # nbins tensor (kept on the tensor itself, shared by every forest lane; one read of the counts)
-    wide = None
-    if dev.type == "cuda" and SPLIT_WIDE:
-        memo = getattr(nbins, "_fdx_wide", None)
-        if memo is None or memo[0] != Fa:
-            idx = np.nonzero(nbins[:Fa].cpu().numpy() > 16)[0].astype(np.int32)
-            memo = (Fa, torch.from_numpy(idx).to(dev))
-            nbins._fdx_wide = memo
-        wide = memo[1]
+    wide = _wide_features(nbins, Fa) if dev.type == "cuda" else None
     C.tree_split_find(hist, totals, boff, nbins, zbin, fid_orig, node_ids, kexp, int(params.mode),
                       float(params.lambda_), float(params.min_child), feat_thr, int(params.seed), int(tree_index),
                       out_gain, out_bin, out_left, node_tree, wide, row_of)
@@ -708,8 +693,9 @@ class LevelState:
         # and the subtraction triples as rows
         self.row_of = [i32(cap), i32(cap)]
         self.dst_row, self.par_row, self.sib_row = i32(cap), i32(cap), i32(cap)
+        # (the partition splits on dense-block features in its row pass, not the CSC column pass)
         self.node_dense = self.hot_row = None
-        if Q.dense is not None and PARTITION_DENSE:
+        if Q.dense is not None:
             hot_row = np.full(Q.Fa, -1, dtype=np.int32)
             hot_row[Q.hot] = np.arange(len(Q.hot), dtype=np.int32)
             self.hot_row = torch.from_numpy(hot_row).to(dev)
@@ -784,55 +770,25 @@ def _feature_mix(Q: Quantized) -> torch.Tensor:
     return t
 
 
-def _gbdt_levels_setup(Q, ws, st, params, runner, rg):
-    """Hands the runner the row-group tables and fixed level buffers of its C++ GBDT level loop
-    (RfLevels.gbdt_setup), once per runner; returns the two level-histogram tensors (the root's
-    is row 0 of the first, zeroed by the prologue)."""
-    key = (RG_DBG, GBDT_CHOOSE_ROWS, LIST_NODE_COUNTS, PARTITION_COUNTS, RG_PARTIALS, RG_PARTIALS_MULTI, SPLIT_WIDE,
-           qmod.RG_LIST_WGS, qmod.RG_ALPHA, qmod.RG_EM_MIN_FRAC)
-    cached = getattr(ws, "_gbdt_levels", None)
-    if cached is not None and cached[0] is runner and cached[2] == key:     # (in-process A/Bs flip these)
-        return cached[1]
-    dev, TB, D = Q.device, Q.TB, int(params.max_depth)
-    # level d opens at most 2^d nodes; even and odd levels alternate between the two tensors
-    rows = [max([1] + [1 << d for d in range(k, D, 2)]) for k in (0, 1)]
-    hists = [torch.empty((r, TB, 2), dtype=torch.int64, device=dev) for r in rows]
-    em = rg.erow is not None and qmod.RG_EM_MIN_FRAC <= 1.0
-    part = ws.rg_part(rg, rg.list_work()) if RG_PARTIALS else None
-    runner.gbdt_setup(dict(
-        rg_wg_list=rg.list_work(), rg_wg_first_list=rg.list_work_first() if RG_PARTIALS else None,
-        rg_ptr=rg.ptr, rg_ent=rg.ent, rg_gbase=rg.gbase, rg_gbin=rg.gbin, rg_gmode=rg.gmode, rg_wg=rg.work(),
-        rg_erow=rg.erow, rg_ebase=int(rg.ebase) if rg.erow is not None else 0,
-        emdig=ws.rg_emdig() if em else None, em_min_rows=max(1, int(qmod.RG_EM_MIN_FRAC * Q.n_rows)),
-        rg_part=part, rg_wg_first=rg.work_first() if RG_PARTIALS else None,
-        list_work=ws.rg_work, rg_start=ws.rg_start, rg_list=ws.rg_list, rg_listdig=ws.rg_listdig,
-        hist_a=hists[0], hist_b=hists[1], packed=torch.empty((1 << (D - 1), 5), dtype=torch.int64, device=dev),
-        one=st.one, zero1=st.zero1, open1=st.open[1], totals1=st.totals[1], boff=Q.boff,
-        wide=_wide_features(Q.nbins, Q.Fa) if SPLIT_WIDE else None, counted=PARTITION_COUNTS, dbg=RG_DBG,
-        part_multi=RG_PARTIALS_MULTI, choose_rows=GBDT_CHOOSE_ROWS, node_counts=LIST_NODE_COUNTS))
-    ws._gbdt_levels = (runner, hists, key)
-    return hists
 # the DP runner calls RCCL directly on the process group's communicator (0: through Python)
 DP_DIRECT_RCCL = os.environ.get("FDX_DP_DIRECT_RCCL", "1") == "1"
 
 
-def _gbdt_dp_setup(Q, ws, st, params, runner, rg, shards, coll) -> torch.Tensor:
-    """Hands the runner its data-parallel GBDT level loop (RfLevels.gbdt_dp_setup): the row-group
-    tables, the shard-major send buffer, the two reduced-level buffers, the feature shard's split
-    tables and the collective callbacks; once per runner. Returns the root level's send region
-    (zeroed by the prologue)."""
-    cached = getattr(ws, "_gbdt_dp", None)
-    if cached is not None and cached[0] is runner:
-        return cached[1]
-    dev, D, S, Bs = Q.device, int(params.max_depth), int(shards.S), int(shards.Bs)
-    widest = max(1 << max(D - 1, 1), 2)
-    send = torch.empty(S * widest * Bs * 2, dtype=torch.int64, device=dev)
-    outs = [torch.empty((widest, Bs, 2), dtype=torch.int64, device=dev) for _ in range(2)]
+def _gbdt_setup(Q, ws, st, params, runner, rg, shards=None, coll=None) -> torch.Tensor:
+    """Hands the runner the row-group tables and fixed level buffers of its C++ GBDT level loop
+    (RfLevels.gbdt_setup), once per runner: one process, the two level-histogram tensors; data
+    parallel (``shards``), the shard-major send buffer, the two reduced-level buffers, the feature
+    shard's split tables and the collectives (RCCL communicator, Python callbacks). Returns what
+    the prologue zeroes for the root level: row 0 of the first histogram tensor, or the root's
+    send region."""
+    key = (RG_DBG, GBDT_CHOOSE_ROWS, PARTITION_COUNTS, RG_PARTIALS, qmod.RG_LIST_WGS, qmod.RG_ALPHA,
+           qmod.RG_EM_MIN_FRAC)
+    cached = getattr(ws, "_gbdt_levels", None)
+    if cached is not None and cached[0] is runner and cached[1] is shards and cached[2] == key:
+        return cached[3]                                                    # (in-process A/Bs flip these)
+    dev, D = Q.device, int(params.max_depth)
     em = rg.erow is not None and qmod.RG_EM_MIN_FRAC <= 1.0
-    cb = _DpCollectives(coll, dev)
-    comm, lib = _rccl_comm(dev)
-    runner.gbdt_dp_setup(dict(
-        comm=comm, rccl_lib=lib,
+    cfg = dict(
         rg_wg_list=rg.list_work(), rg_wg_first_list=rg.list_work_first() if RG_PARTIALS else None,
         rg_ptr=rg.ptr, rg_ent=rg.ent, rg_gbase=rg.gbase, rg_gbin=rg.gbin, rg_gmode=rg.gmode, rg_wg=rg.work(),
         rg_erow=rg.erow, rg_ebase=int(rg.ebase) if rg.erow is not None else 0,
@@ -840,32 +796,34 @@ def _gbdt_dp_setup(Q, ws, st, params, runner, rg, shards, coll) -> torch.Tensor:
         rg_part=ws.rg_part(rg, rg.list_work()) if RG_PARTIALS else None,
         rg_wg_first=rg.work_first() if RG_PARTIALS else None,
         list_work=ws.rg_work, rg_start=ws.rg_start, rg_list=ws.rg_list, rg_listdig=ws.rg_listdig,
-        one=st.one, zero1=st.zero1, open1=st.open[1], totals1=st.totals[1], boff=Q.boff, wide=None,
-        counted=PARTITION_COUNTS, node_counts=LIST_NODE_COUNTS, dbg=RG_DBG, part_multi=RG_PARTIALS_MULTI,
-        rs=cb.rs, ag=cb.ag, mx=cb.mx, S=S, Bs=Bs, bin_lo=shards.bin_lo, send=send, out_a=outs[0], out_b=outs[1],
-        row_of0=st.row_of[0], row_of1=st.row_of[1], ag_in=torch.empty((widest, 5), dtype=torch.int64, device=dev),
-        sboff=shards.boff, snbins=shards.nbins, szbin=shards.zbin, sfid=shards.fid_orig, f0=int(shards.f0),
-        swide=_wide_features(shards.nbins, shards.Fa) if SPLIT_WIDE else None, dst_row=st.dst_row,
-        par_row=st.par_row, sib_row=st.sib_row, iota=ws.iota(64)))
-    root = send[:S * 2 * Bs * 2]
-    ws._gbdt_dp = (runner, root)
-    if runner.dp_direct():
+        one=st.one, zero1=st.zero1, open1=st.open[1], totals1=st.totals[1], boff=Q.boff,
+        counted=PARTITION_COUNTS, dbg=RG_DBG, choose_rows=GBDT_CHOOSE_ROWS)
+    if shards is None:
+        # level d opens at most 2^d nodes; even and odd levels alternate between the two tensors
+        rows = [max([1] + [1 << d for d in range(k, D, 2)]) for k in (0, 1)]
+        hists = [torch.empty((r, Q.TB, 2), dtype=torch.int64, device=dev) for r in rows]
+        cfg.update(hist_a=hists[0], hist_b=hists[1], wide=_wide_features(Q.nbins, Q.Fa),
+                   packed=torch.empty((1 << (D - 1), 5), dtype=torch.int64, device=dev))
+        root = hists[0][:1]
+    else:
+        S, Bs = int(shards.S), int(shards.Bs)
+        widest = max(1 << max(D - 1, 1), 2)
+        send = torch.empty(S * widest * Bs * 2, dtype=torch.int64, device=dev)
+        outs = [torch.empty((widest, Bs, 2), dtype=torch.int64, device=dev) for _ in range(2)]
+        cb = _DpCollectives(coll, dev)
+        comm, lib = _rccl_comm(dev)
+        cfg.update(comm=comm, rccl_lib=lib, rs=cb.rs, ag=cb.ag, mx=cb.mx, S=S, Bs=Bs, bin_lo=shards.bin_lo, send=send,
+                   out_a=outs[0], out_b=outs[1], row_of0=st.row_of[0], row_of1=st.row_of[1],
+                   ag_in=torch.empty((widest, 5), dtype=torch.int64, device=dev), sboff=shards.boff,
+                   snbins=shards.nbins, szbin=shards.zbin, sfid=shards.fid_orig, f0=int(shards.f0),
+                   swide=_wide_features(shards.nbins, shards.Fa), dst_row=st.dst_row, par_row=st.par_row,
+                   sib_row=st.sib_row, iota=ws.iota(64))
+        root = send[:S * 2 * Bs * 2]
+    runner.gbdt_setup(cfg)
+    ws._gbdt_levels = (runner, shards, key, root)
+    if shards is not None and runner.dp_direct() and runner not in _DP_RUNNERS:
         _DP_RUNNERS.append(runner)
     return root
-
-
-def _gbdt_runner_levels(Q, runner, tree_index, on_first_wait):
-    """The level loop of a single-process GBDT tree in the runner (C++): level 0 is queued, the
-    previous tree's host table is built while it runs (on_first_wait), then levels 1.. run with
-    the host waits inside the runner. Same launches and trees as the generic loop."""
-    runner.gbdt_root(tree_index)
-    if on_first_wait is not None:
-        on_first_wait()
-    shape = runner.gbdt_levels(tree_index)
-    for j in range(0, len(shape), 2):
-        LEVEL_STATS["levels"] += 1
-        LEVEL_STATS["built_nodes"] += shape[j + 1]
-        LEVEL_STATS["hist_bytes"] += shape[j + 1] * Q.TB * 16
 
 
 def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int, g: torch.Tensor,
@@ -896,11 +854,11 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
     np_ = _choose_np(params, weight)
     mode_rs = 0 if params.mode == 0 else 1
     build_all = bool(params.feat_k)
-    sampled = SAMPLED and build_all and np_ == 1
+    sampled = build_all and np_ == 1
     # RF levels >= 1: the next level's feature sample and its active-item lists are queued right
     # after the plan, so the per-XCD item counts reach the host with the level's counts and each
     # histogram pass launches one wave per active item (no grid of ~300K mostly idle wave slots)
-    presel = PRESELECT and sampled and dev.type == "cuda" and Q.n_rows >= PRESELECT_MIN_ROWS
+    presel = PRESELECT and sampled and dev.type == "cuda"
     item_groups = (Q.groups + Q.hot_groups) if sampled else []
     sel_ids = [gi for gi, grp in enumerate(item_groups) if grp.num_items] if presel else []
     sel_args = None
@@ -923,27 +881,23 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
     # the next level's zeroed histograms (at most 2 open nodes per open node) are queued before
     # the host waits for its counts, so the fill runs while the host sizes that level
     pre_hist = None
-    # single-process GBDT rounds on the row-group engine: the level loop runs in the runner
-    rg_cxx = ws.rowgroups() if (native_prologue and gbdt_native and GBDT_CXX_LEVELS and SPLIT_SUBTRACT and
-                                np_ == 4 and margin is not None and g is None) else None
-    # data-parallel GBDT rounds on the row-group engine: the same runner loop around the level
-    # collectives (RfLevels.gbdt_dp_levels; the collectives are Python callbacks)
-    rg_dp = ws.rowgroups() if (runner is not None and shards is not None and gbdt_native and GBDT_CXX_LEVELS and
-                               SPLIT_SUBTRACT and np_ == 4 and margin is not None and g is None) else None
-    if rg_dp is not None:
+    # GBDT rounds on the row-group engine, in one process or data parallel: the level loop runs in
+    # the runner (RfLevels.gbdt_levels; data parallel: around the level's collectives, RCCL called
+    # by the runner or Python callbacks)
+    dp = shards is not None
+    rg_native = ws.rowgroups() if (runner is not None and (dp or native_prologue) and gbdt_native and
+                                   GBDT_CXX_LEVELS and np_ == 4 and margin is not None and g is None) else None
+    if rg_native is not None:
         with tracing.span("tree.quant"):
-            root_zero = _gbdt_dp_setup(Q, ws, st, params, runner, rg_dp, shards, coll)
+            root_zero = _gbdt_setup(Q, ws, st, params, runner, rg_native, shards, coll)
             g, h = ws.gh()
-            # gradients + max slots (all-reduced by the runner's callback) + arena image + the root's
-            # send region zeroed, then the quantisation
+            # gradients + max |g|, |h| (data parallel: all-reduced by the runner) + arena image + the
+            # root histogram (data parallel: the root's send region) zeroed, then the quantisation
             runner.prologue(margin, g, h, label, None, int(tree_index), False, 4, None, ws.totals, None, Q.row0,
                             root_zero, st.arena_init_dev)
     elif native_prologue:
         # the root histogram is zeroed by the prologue's first launch
-        if rg_cxx is not None:
-            pre_hist = _gbdt_levels_setup(Q, ws, st, params, runner, rg_cxx)[0][:1]
-        else:
-            pre_hist = torch.empty((1, TB, 2), dtype=torch.int64, device=dev)
+        pre_hist = torch.empty((1, TB, 2), dtype=torch.int64, device=dev)
         with tracing.span("tree.quant"):
             # (the dense-block digit planes only feed the MFMA dense path, off with the row groups)
             digp = ws.digp if (ws.digp is not None and not build_all and ws.rowgroups() is None) else None
@@ -969,7 +923,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
             C.tree_logistic_grad(margin, label, weight, g, h)
         ws.row_node.zero_()
     with tracing.span("tree.quant"):
-        if native_prologue or rg_dp is not None:
+        if native_prologue or rg_native is not None:
             pass
         elif np_ == 4:
             C.tree_quant_max(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, Q.n_rows,
@@ -982,7 +936,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                          ws.kexp, ws.totals, ws.digp, Q.row0)
     # root: node 0, open list [0] with the exact totals (no host round trip); under data
     # parallelism the totals are summed by the root level's reduce-scatter (LaneBufs.tot_bin)
-    if not native_prologue and rg_dp is None:
+    if not native_prologue and rg_native is None:
         st.arena.copy_(st.arena_init, non_blocking=True)
         st.open[0][:1].zero_()
     if shards is None and not native_prologue:
@@ -1003,16 +957,15 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                               Q.fid_orig)
         yield st.record_event(cur_stream)
     generic_depth = params.max_depth
-    if rg_cxx is not None:
-        _gbdt_runner_levels(Q, runner, int(tree_index), on_first_wait)
-        on_first_wait = None
-        generic_depth = 0
-    elif rg_dp is not None:
-        runner.gbdt_dp_root(int(tree_index))
+    if rg_native is not None:
+        # level 0 is queued, the previous tree's host table is built while it runs (on_first_wait),
+        # then levels 1.. run with the host waits inside the runner: same launches and trees as the
+        # generic loop below
+        runner.gbdt_root(int(tree_index))
         if on_first_wait is not None:
             on_first_wait()
             on_first_wait = None
-        shape = runner.gbdt_dp_levels(int(tree_index))
+        shape = runner.gbdt_levels(int(tree_index))
         for j in range(0, len(shape), 2):
             LEVEL_STATS["levels"] += 1
             LEVEL_STATS["built_nodes"] += shape[j + 1]
@@ -1111,13 +1064,12 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
             sel_groups = None
             if rg is not None:
                 shard_args = (shards.bin_lo, bufs.shard_bins) if shards is not None else (None, 0)
-                # single-slot passes: per-workgroup partial tables summed by one reduction instead
-                # of every workgroup's atomics on the same bins (RgHistArgs part)
+                # per-workgroup partial tables summed by one reduction instead of every workgroup's
+                # atomics on the same bins (RgHistArgs part)
                 # (the listed levels have their own, smaller work table: RowGroups.list_work)
                 wtab = rg.work() if d == 0 else rg.list_work()
                 part = dict(part=ws.rg_part(rg, rg.list_work()), wg_first=rg.work_first() if d == 0 else
-                            rg.list_work_first()) \
-                    if (RG_PARTIALS and (n_build == 1 or RG_PARTIALS_MULTI) and dev.type == "cuda") else {}
+                            rg.list_work_first()) if (RG_PARTIALS and dev.type == "cuda") else {}
                 if d == 0:
                     C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, np_, None, None, None, 1, rg.gmode,
                                    wtab, s2n, hist_target, h_stride, *shard_args, RG_DBG, **rg.em_args(), **part)
@@ -1213,7 +1165,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                     assert n_build + n_sub == n_open, (d, n_build, n_sub, n_open)
                 cur_hist = bufs.out
         # (single-process runner levels subtract inside the split search: split_plan prev_hist)
-        fused_sub = runner is not None and shards is None and d > 0 and not build_all and SPLIT_SUBTRACT
+        fused_sub = runner is not None and shards is None and d > 0 and not build_all
         if d > 0 and not build_all and not fused_sub:
             if shards is None:
                 C.tree_hist_subtract(prev_hist, cur_hist, st.sub_dst[:n_build], st.sub_par[:n_build],
@@ -1230,7 +1182,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
             elif runner is not None:
                 runner.split(cur_hist, totals_d, split_boff, shards.nbins, shards.zbin, shards.fid_orig, open_d,
                              feat_thr, int(tree_index), shards.f0, bufs.ag_in, row_of,
-                             _wide_features(shards.nbins, shards.Fa) if SPLIT_WIDE else None)
+                             _wide_features(shards.nbins, shards.Fa))
                 packed = yield CollStep("ag")
             elif shards is None:
                 packed = _best_splits(C, cur_hist, totals_d, Q.boff, Q.nbins, Q.zbin, Q.fid_orig, open_d, ws.kexp,
@@ -1264,7 +1216,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                 sel = []
             if shards is None:
                 runner.split_plan(d, n_open, cur_hist, totals_d, Q.boff, feat_thr, int(tree_index), packed,
-                                  _wide_features(Q.nbins, Q.Fa) if SPLIT_WIDE else None, open_d, n_open_ptr,
+                                  _wide_features(Q.nbins, Q.Fa), open_d, n_open_ptr,
                                   st.open[nxt], st.totals[nxt], sample_next, thr_n, mask_n, sel,
                                   prev_hist if fused_sub else None)
             else:
@@ -1321,7 +1273,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
     if on_first_wait is not None:          # (a one-level tree) the previous table first
         on_first_wait()
     # one read of the node table per tree: the arena (table + exponents) in one D2H copy, one wait
-    if not native_prologue and rg_dp is None:      # (the prologue's quantisation wrote them)
+    if not native_prologue and rg_native is None:      # (the prologue's quantisation wrote them)
         st.kexp_slot.copy_(ws.kexp)
     node_value = None
     if deferred and params.mode == 0:
@@ -1371,7 +1323,7 @@ def _partition_stage(Q: Quantized, stg, default_child: np.ndarray, splits: list,
     # row, coalesced) instead of scattering the column's millions of CSC entries
     node_dense = None
     col_splits = splits
-    if Q.dense is not None and PARTITION_DENSE:
+    if Q.dense is not None:
         if getattr(Q, "_hot_row", None) is None:
             Q._hot_row = np.full(Q.Fa, -1, dtype=np.int32)
             Q._hot_row[Q.hot] = np.arange(len(Q.hot), dtype=np.int32)

@@ -170,7 +170,7 @@ def test_gpu_gbdt_large_shard_paths_equal_host(monkeypatch):
     assert C.tree_rg_list_rows(5000) == 512
 
 
-def _dp_booster(rank, world, device, cxx, direct=True, big=False):
+def _dp_booster(rank, world, device, cxx, direct=True, big=False, depth=6):
     """One rank's booster under data parallelism, with its collective calls counted (big: the
     >4M-row list regime on this small shard -- 2048-row list waves, the partition's per-node
     counts instead of the lists' counting pass)."""
@@ -183,29 +183,32 @@ def _dp_booster(rank, world, device, cxx, direct=True, big=False):
     grower.DP_DIRECT_RCCL = direct
     lo, hi = D.shard_range(5000, rank, world)
     D.reset_bytes()
-    trees = _booster(device, rows=(lo, hi))
+    trees = _booster(device, depth=depth, rows=(lo, hi))
     return trees, dict(D.CALLS), grower.LEVEL_STATS["coll_calls"]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,backend", [(1, "nccl"), (2, "gloo")])
 def test_gpu_gbdt_dp_runner_levels_equal_single_process(world, backend, monkeypatch):
-    """the data-parallel GBDT level loop in the runner (RfLevels.gbdt_dp_levels:
-    the level's reduce-scatter / all-gather / the quantisation max as callbacks, the sibling
-    subtraction inside the shard's split search) grows the single-process trees bit for bit -- at
-    world 1 through RCCL and at world 2 (two ranks on this GPU over gloo: 2 feature shards) -- as
-    does the Python-issued DP level loop; 13 collectives per tree."""
+    """the data-parallel GBDT level loop in the runner (RfLevels.gbdt_root /
+    gbdt_levels set up with the DP keys: the level's reduce-scatter / all-gather / the quantisation
+    max through RCCL or as callbacks, the sibling subtraction inside the shard's split search) grows
+    the single-process trees bit for bit -- at world 1 through RCCL and at world 2 (two ranks on
+    this GPU over gloo: 2 feature shards) -- as does the Python-issued DP level loop; 13 collectives
+    per tree. Depth 1 is a root-only tree: gbdt_root alone, the root totals riding in its
+    reduce-scatter, no gbdt_levels iteration."""
     from fraud_detection_spark_kafka_llm_amd.parallel.launch import spawn
 
-    ref = _booster("cuda:0")
+    refs = {6: _booster("cuda:0"), 1: _booster("cuda:0", depth=1)}
     monkeypatch.setenv("FDX_FORCE_COLLECTIVES", "1")
     trees = 8
     # (the runner calls RCCL itself on the process group's communicator; direct=False: through
     # the Python callbacks, as on gloo)
-    for cxx, direct, big in ((True, True, False), (True, False, False), (False, True, False), (True, True, True)):
-        outs = spawn(_dp_booster, world, "cuda:0", cxx, direct, big, backend=backend)
+    for cxx, direct, big, depth in ((True, True, False, 6), (True, False, False, 6), (False, True, False, 6),
+                                    (True, True, True, 6), (True, True, False, 1)):
+        outs = spawn(_dp_booster, world, "cuda:0", cxx, direct, big, depth, backend=backend)
         for got, calls, level_calls in outs:
-            assert got == ref, (cxx, direct, big, world)
+            assert got == refs[depth], (cxx, direct, big, depth, world)
             assert level_calls > 0
             # (+ fit_gbdt's base score and the quantisation's max / key gathers)
             assert calls["reduce_scatter"] + calls["all_gather"] <= 12 * trees + 4, calls
