@@ -1661,6 +1661,11 @@ class RfBatch {
       allt = buffer(allt_, S_ * nopen * 5).view({S_, nopen, 5});
       FDX_CHECK(hipMemsetAsync(send.data_ptr(), 0, send.nbytes(), s) == hipSuccess, "send zero");
     }
+    // Without preselected lists a level is one listed pass or one plain pass for the whole batch
+    // (launch_hist_lanes: every lane of a launch takes the same kernel): listed only while every
+    // live lane has few open nodes; the plain pass counts any number of nodes to the same histogram.
+    bool listed_level = true;
+    for (int l : live_) listed_level = listed_level && lanes_[l].n_open <= listed_max_;
     for (int l : live_) {
       Lane& ln = lanes_[l];
       std::vector<optional<Tensor>> lists, cnts;
@@ -1673,7 +1678,7 @@ class RfBatch {
             return ln.r->st_["counts"].select(0, d - 1).narrow(0, 4 + 8 * ln.sel_j[gi], 8);
           }));
           npxs.push_back(ln.npx[gi]);
-        } else if (items && ln.n_open <= listed_max_) {
+        } else if (items && listed_level) {
           lists.push_back(ln.listed[gi]);
           cnts.push_back(ln.listed_cnt[gi]);
           npxs.push_back(-1);

@@ -88,12 +88,29 @@ class ForestLanes:
         return self.switches[i]
 
 
-def batch_ok(Q: Quantized, params: GrowParams, weight) -> bool:
+def batch_ok(Q: Quantized, params: GrowParams, weight, coll=None) -> bool:
     """The lockstep batch covers the default sampled-RF configuration on the device (the lean
     runner level loop with fused packed row state and the LDS-atomic count passes)."""
     return (BATCH and Q.device.type == "cuda" and G.NATIVE_LEVELS and G.FUSED_PACK and
             G.RF_LDS and params.feat_k > 0 and G._choose_np(params, weight) == 1 and params.max_depth >= 1 and
-            G.device_levels_ok(params, weight))
+            G.device_levels_ok(params, weight) and
+            lds_counts_fit(Q, params.max_depth, every_rank=coll is not None and coll.active))
+
+
+# the LDS-atomic count kernel's budget in (row tiles of an item group) x (nodes built at a level)
+LDS_TILE_NODES = 128
+
+
+def lds_counts_fit(Q: Quantized, max_depth: int, every_rank: bool = False) -> bool:
+    """Whether every level of a depth-``max_depth`` sampled tree fits the LDS-atomic count kernel,
+    the only histogram kernel the batch records. Mirrors RfLevels::hist (csrc/bindings_level.cpp,
+    ``a.lds = lds_ && 4 * 16 * g.bt * n_build * 8 <= 65536``, i.e. bt * n_build <= 128): the deepest
+    level builds up to 2^(max_depth - 1) nodes. Deeper or wider forests grow on the per-tree lanes,
+    whose runner falls back to the MFMA kernel for such a level. ``every_rank``: the item groups
+    depend on the rank's own rows (packing), and under data parallelism every rank must take the
+    same path, so the widest item there is (4 row tiles) decides."""
+    bt = 4 if every_rank else max((int(g.bt) for g in Q.groups + Q.hot_groups if g.num_items), default=1)
+    return bt * (1 << (max(int(max_depth), 1) - 1)) <= LDS_TILE_NODES
 
 
 class ForestBatch:
@@ -313,7 +330,7 @@ def grow_forest_concurrent(Q: Quantized, lanes: ForestLanes, params: GrowParams,
     order so that every rank issues the same collective sequence."""
     cuda = lanes.dev.type == "cuda"
     use_coll = coll is not None and coll.active
-    if batch_ok(Q, params, weight):
+    if batch_ok(Q, params, weight, coll):
         return grow_forest_batched(Q, lanes, params, tree_ids, label, weight, bootstrap, coll)
     shards = build_shared_state(Q, lanes, coll if use_coll else None)
     if cuda:                                   # the lanes see everything queued before (Q, label, shared state)

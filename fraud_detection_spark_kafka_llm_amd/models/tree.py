@@ -137,7 +137,8 @@ def fit_forest(features, labels, num_trees: int = 1, max_depth: int = 5, max_bin
     lanes = None
     left = num_trees - len(trees)
     # (on the device every sampled forest, a single tree too, grows on the lockstep batch)
-    if left > 0 and device_levels_ok(params, w) and (forest_batch.batch_ok(Q, params, w) or (inflight > 1 and left > 1)):
+    if left > 0 and device_levels_ok(params, w) and (forest_batch.batch_ok(Q, params, w, coll) or
+                                                     (inflight > 1 and left > 1)):
         with tracing.span("forest.lanes"):
             lanes = ForestLanes(Q, max(1, min(inflight, left)), ws)
     chunk = max(ckpt.every if ckpt is not None else 64, 1)

@@ -1,6 +1,8 @@
 """The native per-level runner (csrc/bindings_level.cpp RfLevels) and the kernels it brought:
 same forests and boosters as the Python-driven levels, multi-workgroup compact layout equal to
 the host twin."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -8,22 +10,86 @@ import torch
 from fraud_detection_spark_kafka_llm_amd.ops import native
 
 
-def _forest(device, n=6000, F=400, trees=6, depth=5, seed=7, rows=None):
-    from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
-    from fraud_detection_spark_kafka_llm_amd.models.tree import fit_forest
-
+@functools.lru_cache(maxsize=None)
+def _data(kind, n, F, seed, hi):
+    """(counts [n, F], labels [n]) of the forests' inputs (read-only: shared between tests).
+    "skewed": Zipf-like presence, counts 1..3, an XOR label with 5% flips. "pure side": the same
+    counts, y = (c1 > 0) & ((c5 >= 2) ^ noise): the rows without feature 1 are all class 0, so
+    trees that split on it first stop on one side and the trees of a batch differ in shape.
+    "full": every feature present in 90% of the rows with counts 1..hi-1, coin-flip labels: every
+    feature has hi bins and the trees stay wide down to the last level."""
     rng = np.random.default_rng(seed)
+    if kind == "full":
+        counts = (rng.random((n, F)) < 0.9) * rng.integers(1, hi, (n, F))
+        return counts, (rng.random(n) < 0.5).astype(np.float32)
     p = 0.5 / (1.0 + np.arange(F)) ** 0.7
     counts = (rng.random((n, F)) < p) * rng.integers(1, 4, (n, F))
+    if kind == "pure side":
+        noise = rng.random(n) < 0.1
+        return counts, ((counts[:, 1] > 0) & ((counts[:, 5] >= 2) ^ noise)).astype(np.float32)
     y = ((counts[:, 1] > 0) ^ (counts[:, 5] >= 2)).astype(np.float32)
     flip = rng.random(n) < 0.05
     y[flip] = 1 - y[flip]
+    return counts, y
+
+
+def _fit(device, n=6000, F=400, trees=6, depth=5, seed=7, rows=None, data="skewed", hi=60, max_bins=32,
+         min_instances=1, prune=True):
+    from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
+    from fraud_detection_spark_kafka_llm_amd.models.tree import fit_forest
+
+    counts, y = _data(data, n, F, seed, hi)
     if rows is not None:                                     # (this rank's shard)
         counts, y = counts[rows[0]:rows[1]], y[rows[0]:rows[1]]
     vc = VectorColumn(F, dense=torch.from_numpy(counts.astype(np.float64)))
-    r = fit_forest(vc, torch.from_numpy(y), num_trees=trees, max_depth=depth, bootstrap=True, feature_subset="sqrt",
-                   seed=seed, device=device)
+    return fit_forest(vc, torch.from_numpy(y.copy()), num_trees=trees, max_depth=depth, max_bins=max_bins,
+                      min_instances=min_instances, bootstrap=True, feature_subset="sqrt", seed=seed, device=device,
+                      prune=prune)
+
+
+def _lists(r):
     return [(t.feature.tolist(), t.threshold.tolist(), t.stats.tolist()) for t in r.trees]
+
+
+def _forest(device, **kw):
+    return _lists(_fit(device, **kw))
+
+
+def _split_nodes(t):
+    """Split (internal) nodes of a tree per depth."""
+    out, stack = {}, [(t.root, 0)]
+    while stack:
+        i, d = stack.pop()
+        if t.feature[i] >= 0:
+            out[d] = out.get(d, 0) + 1
+            stack += [(int(t.left[i]), d + 1), (int(t.right[i]), d + 1)]
+    return out
+
+
+def _item_tiles(max_bins, **kw):
+    """Row tiles (bt) of the non-empty histogram item groups of an input."""
+    from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
+    from fraud_detection_spark_kafka_llm_amd.models.tree import prepare
+
+    counts, y = _data(kw["data"], kw["n"], kw["F"], kw.get("seed", 7), kw.get("hi", 60))
+    vc = VectorColumn(kw["F"], dense=torch.from_numpy(counts.astype(np.float64)))
+    Q = prepare(vc, torch.from_numpy(y.copy()), "cpu", max_bins)[0]
+    return [int(g.bt) for g in Q.groups + Q.hot_groups if g.num_items]
+
+
+def _count_batches(monkeypatch):
+    """Counts the forests grown on the lockstep batch (forest_batch.grow_forest_batched)."""
+    from fraud_detection_spark_kafka_llm_amd.models import forest_batch
+
+    calls = []
+    real = forest_batch.grow_forest_batched
+
+    def spy(*a, **k):
+        calls.append(1)
+        return real(*a, **k)
+
+    monkeypatch.setattr(forest_batch, "grow_forest_batched", spy)
+    return calls
 
 
 @pytest.mark.gpu
@@ -61,6 +127,84 @@ def test_gpu_rf_lockstep_batch_equals_per_tree_lanes(inflight, depth, monkeypatc
         ref = _forest("cuda:0", trees=7, depth=depth)
         monkeypatch.setattr(forest_batch, "BATCH", True)
         assert _forest("cuda:0", trees=7, depth=depth) == ref, presel
+
+
+FULL = dict(data="full", n=4000, F=64, trees=5)
+
+
+@pytest.mark.gpu
+def test_gpu_rf_beyond_the_lds_budget_equals_per_tree_forest(monkeypatch):
+    """The LDS-atomic count kernel, the only histogram kernel the lockstep batch records, holds
+    bt * n_build <= 128 (row tiles of an item group x nodes built at a level; RfLevels::hist in
+    csrc/bindings_level.cpp). Depth 7 over features of more than 32 bins (bt = 4) builds up to 64
+    nodes at the last level: the default path must grow that forest and give, bit for bit, the
+    per-tree lanes' forest, the Python-issued levels' and the host's."""
+    from fraud_detection_spark_kafka_llm_amd.models import forest_batch, grower
+
+    kw = dict(depth=7, max_bins=64, prune=False, **FULL)
+    host = _fit("cpu", **kw)
+    tiles = _item_tiles(64, **FULL)
+    widest = max(_split_nodes(t).get(6, 0) for t in host.trees)
+    assert tiles and set(tiles) == {4} and widest > 32, (tiles, widest)       # 4 * (> 32) > 128
+    ref = _lists(host)
+    assert _forest("cuda:0", **kw) == ref                    # the default configuration
+    monkeypatch.setattr(forest_batch, "BATCH", False)
+    assert _forest("cuda:0", **kw) == ref
+    monkeypatch.setattr(forest_batch, "BATCH", True)
+    monkeypatch.setattr(grower, "NATIVE_LEVELS", False)
+    assert _forest("cuda:0", **kw) == ref
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth,max_bins,hi,bt", [(6, 64, 60, 4), (7, 32, 31, 2)])
+def test_gpu_rf_at_the_lds_budget_stays_on_the_batch(depth, max_bins, hi, bt, monkeypatch):
+    """bt * 2^(depth - 1) = 128 exactly (4 x 32 and 2 x 64): still the lockstep batch, and the
+    per-tree lanes' forest and the host's bit for bit."""
+    from fraud_detection_spark_kafka_llm_amd.models import forest_batch
+
+    kw = dict(depth=depth, max_bins=max_bins, hi=hi, prune=False, **FULL)
+    tiles = _item_tiles(max_bins, hi=hi, **FULL)
+    assert tiles and set(tiles) == {bt} and bt * 2 ** (depth - 1) == 128, tiles
+    calls = _count_batches(monkeypatch)
+    got = _forest("cuda:0", **kw)
+    assert len(calls) == 1, "the forest left the lockstep batch"
+    monkeypatch.setattr(forest_batch, "BATCH", False)
+    assert _forest("cuda:0", **kw) == got
+    assert len(calls) == 1
+    assert _forest("cpu", **kw) == got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("min_instances", [1, 40])
+def test_gpu_rf_lockstep_batch_of_differently_shaped_trees(min_instances, monkeypatch):
+    """Trees of one batch with different numbers of open nodes at a level, around the listed
+    pass's threshold (grower.LISTED_MAX_NODES = 2): a lane-batched launch is one kernel for every
+    lane, so the listed / plain choice is the batch-level's, not the lane's. With and without
+    preselected item lists the batch grows the per-tree lanes' forest and the host's. min_instances
+    40 keeps every lane at or under the threshold with differing node counts."""
+    from fraud_detection_spark_kafka_llm_amd.models import forest_batch, grower
+
+    kw = dict(data="pure side", trees=7, depth=5, prune=False, min_instances=min_instances)
+    host = _fit("cpu", **kw)
+    shapes = [_split_nodes(t) for t in host.trees]
+    if min_instances == 1:
+        one = [i for i, s in enumerate(shapes) if s.get(1, 0) == 1]
+        wide = [i for i, s in enumerate(shapes) if s.get(2, 0) >= 3]
+        assert one and set(wide) - set(one), shapes          # <= 2 and > 2 open nodes at one level
+    else:
+        per_level = [{s.get(d, 0) for s in shapes} for d in range(5)]
+        assert max(max(p) for p in per_level) == 2 and any(len(p) > 1 for p in per_level), shapes
+    ref = _lists(host)
+    monkeypatch.setattr(forest_batch, "TREES_IN_FLIGHT", 8)  # all seven trees in one batch
+    calls = _count_batches(monkeypatch)
+    for presel in (True, False):
+        monkeypatch.setattr(grower, "PRESELECT", presel)
+        monkeypatch.setattr(forest_batch, "BATCH", False)
+        assert _forest("cuda:0", **kw) == ref, presel
+        n = len(calls)
+        monkeypatch.setattr(forest_batch, "BATCH", True)
+        assert _forest("cuda:0", **kw) == ref, presel
+        assert len(calls) == n + 1, "the forest left the lockstep batch"
 
 
 def _dp_forest(rank, world, device, batch, compact):

@@ -52,6 +52,34 @@ def test_no_cut_inside_a_giant_word():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("scorer", ["lr", "trees"])
+def test_gpu_scorer_slot_at_the_streaming_capacities(scorer):
+    """The streaming scorer routes by raw bytes (gpu_worker.LONG_DOC_MIN): a 3,000-byte dialogue of
+    1,500 kept tokens overflows the streaming kernel's token table without ever being given to the
+    long-dialogue kernel, and collect() finishes it on the host; dialogues of exactly 4096 and 4097
+    bytes stand on either side of the routing. The slot scores bitwise as the host scorer."""
+    from fraud_detection_spark_kafka_llm_amd.stream.gpu_worker import LONG_DOC_MIN, GpuScorer, HostScorer
+    from fraud_detection_spark_kafka_llm_amd.stream.ring import PinnedRing
+    from test_text_featurizer import random_docs, random_forest_arrays
+
+    F = 1 << 12
+    rng = np.random.default_rng(9)
+    spec = FeatureSpec(clean=True, stopwords=["the", "a"], num_features=F)
+    docs = ["b " * 1500, "word " * 819 + "x", "word " * 819 + "xy"] + random_docs(5, seed=6)
+    nb = [len(d.encode()) for d in docs]
+    assert nb[0] < LONG_DOC_MIN == nb[1] == nb[2] - 1
+    idf = rng.random(F)
+    model = LinearScorer(rng.standard_normal(F), 0.5) if scorer == "lr" else random_forest_arrays(70, F, 5, 1, seed=4)
+    ring = PinnedRing(slots=1, max_docs=16, max_bytes=1 << 16)
+    ring.slots[0].fill(docs)
+    gpu = GpuScorer(spec, idf, model, "cuda:0", max_docs=16, max_bytes=1 << 16)
+    host = HostScorer(spec, idf, model, max_docs=16, max_bytes=1 << 16)
+    want = host.score_packed(ring.slots[0])
+    np.testing.assert_array_equal(gpu.score_packed(ring.slots[0]), want)
+    assert want.shape == (len(docs), 1) and np.all(np.isfinite(want))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("clean", [True, False])
 def test_gpu_one_megabyte_dialogue_bitwise_equals_host(clean):
     from fraud_detection_spark_kafka_llm_amd.ml.tree_model import Tree, ensemble_arrays

@@ -1,6 +1,8 @@
 """Row-group histogram engine (csrc/row_kernels.hip, models/quantize.RowGroups): layout coverage,
 exact histograms against the numpy int64 reference on the host and bitwise host == GPU, and the
 level loop growing the CSC passes' trees."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -197,6 +199,124 @@ def _csr_vc_wide(n=3000, F=7000, per_row=120, maxc=60, seed=4):
                               torch.from_numpy(cnt.reshape(-1).astype(np.int32)), torch.ones(F, dtype=torch.float64))
 
 
+RG_STAGE = 2048          # csrc/row_kernels.hip kRgStage: a 16-row wave stages up to this many entries in LDS
+STAGE_CYCLE = (0, 1600, 2047, 2048, 2049, 2304, 3200, 2048, 16, 2049)
+
+
+@functools.lru_cache(maxsize=None)
+def _csr_stage_arrays(F=3000, seed=13):
+    """CSR rows whose 16-row waves hold STAGE_CYCLE entries, twelve times over, then a tail wave of
+    5 rows of 128: waves under, at and over the staging threshold of the wave-per-16-rows build,
+    an empty wave and a short one. A wave's total is spread over its rows as evenly as possible in
+    shuffled order; columns without replacement, popularity ~ 1 / (1 + i)^0.8; counts 1..59."""
+    rng = np.random.default_rng(seed)
+    per_row = []
+    for total in STAGE_CYCLE * 12:
+        rows = np.full(16, total // 16) + (np.arange(16) < total % 16)
+        per_row.append(rng.permutation(rows))
+    per_row = np.concatenate(per_row + [np.full(5, 128)]).astype(np.int64)
+    p = 1.0 / (1.0 + np.arange(F)) ** 0.8
+    p /= p.sum()
+    cols = np.concatenate([np.sort(rng.choice(F, k, replace=False, p=p)) for k in per_row]).astype(np.int32)
+    cnt = rng.integers(1, 60, cols.size).astype(np.int32)
+    indptr = np.concatenate([[0], np.cumsum(per_row)]).astype(np.int64)
+    return indptr, cols, cnt
+
+
+def _csr_vc_stage(dtype=torch.int32, F=3000):
+    from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
+
+    indptr, cols, cnt = _csr_stage_arrays(F)
+    return VectorColumn.tfidf(F, torch.from_numpy(indptr.copy()), torch.from_numpy(cols.copy()),
+                              torch.from_numpy(cnt.copy()).to(dtype), torch.ones(F, dtype=torch.float64))
+
+
+def _stage_waves(vc, Q):
+    """Entries per 16-row wave of the CSR build; every entry is of an active feature, so these are
+    the totals the kernel compares with its staging capacity."""
+    indptr = vc.indptr.cpu().numpy()
+    assert Q.Fa == vc.size and int(indptr[-1]) == int(Q.colptr[-1])
+    starts = np.arange(0, indptr.size - 1, 16)
+    return indptr[np.minimum(starts + 16, indptr.size - 1)] - indptr[starts], (indptr.size - 1) % 16
+
+
+def _rg_runs(rg):
+    """(ptr, the entry runs, the entry-major rows of the runs) without the alignment padding."""
+    ptr, ent, gb = rg.ptr.cpu().numpy(), rg.ent.cpu().numpy(), rg.gbase.cpu().numpy()
+    runs = np.concatenate([ent[gb[g]: gb[g] + ptr[g, -1]] for g in range(rg.G)])
+    er = rg.erow.cpu().numpy()
+    erow = np.concatenate([er[gb[g] - rg.ebase: gb[g] - rg.ebase + ptr[g, -1]] for g in range(rg.em_g0, rg.G)])
+    return ptr, runs, erow
+
+
+def test_row_groups_from_csr_across_the_staging_threshold_equal_csc_build():
+    """Waves of 2047, 2048 and 2049 entries, empty and short ones: the CSR build gives the CSC
+    build's ptr, entry-major rows and the same entries in every (group, row) run."""
+    vc = _csr_vc_stage()
+    Q = quantize(vc, max_bins=64, counts=vc.tf_counts, scale=vc.tf_scale)
+    waves, tail = _stage_waves(vc, Q)
+    assert {0, RG_STAGE - 1, RG_STAGE, RG_STAGE + 1} <= set(waves.tolist()) and tail == 5
+    a = RowGroups(Q, bins=4096)
+    csr = Q.csr_src
+    del Q.csr_src
+    b = RowGroups(Q, bins=4096)
+    Q.csr_src = csr
+    assert a.complete and 2 <= a.G == b.G <= 64 and a.em_g0 == b.em_g0 < a.G and a.erow is not None
+    pa, _, erow_a = _rg_runs(a)
+    pb, _, erow_b = _rg_runs(b)
+    np.testing.assert_array_equal(pa, pb)
+    np.testing.assert_array_equal(erow_a, erow_b)
+    assert int(pa[:, -1].sum()) == int(vc.indptr[-1])         # every entry placed
+    ga, ea, eb = a.gbase.numpy(), a.ent.numpy(), b.ent.numpy()
+    for g in range(a.G):                   # every (group, row) run: the same entries, sorted in the run
+        run = np.repeat(np.arange(Q.n_rows), np.diff(pa[g]))
+        xa, xb = ea[ga[g]: ga[g] + pa[g, -1]], eb[ga[g]: ga[g] + pa[g, -1]]
+        np.testing.assert_array_equal(xa[np.lexsort((xa, run))], xb[np.lexsort((xb, run))])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.int32, torch.float32])
+def test_gpu_row_groups_from_csr_across_the_staging_threshold_equal_host(dtype):
+    """rg_build_csr_wave stages a wave's entries in LDS up to kRgStage (2048) and stores directly
+    beyond: waves at 2047 / 2048 (staged) and 2049 (direct), an empty wave and a 5-row tail write
+    the host twin's ptr, entries and entry-major rows bit for bit."""
+    vc = _csr_vc_stage(dtype)
+    out = []
+    for dev in ("cpu", "cuda:0"):
+        v = vc.to(dev)
+        Q = quantize(v, max_bins=64, counts=v.tf_counts, scale=v.tf_scale)
+        assert getattr(Q, "csr_src", None) is not None
+        waves, tail = _stage_waves(v, Q)
+        assert (waves == RG_STAGE).sum() >= 1 and (waves == RG_STAGE + 1).sum() >= 1
+        assert ((waves > 0) & (waves < RG_STAGE)).any() and (waves > RG_STAGE + 1).any()
+        assert (waves == 0).any() and 0 < tail < 16
+        rg = RowGroups(Q, bins=4096)
+        assert rg.complete and rg.erow is not None and rg.em_g0 < rg.G
+        out.append(_rg_runs(rg) + (rg.G,))
+    assert out[0][3] == out[1][3] >= 2
+    for k in range(3):
+        np.testing.assert_array_equal(out[0][k], out[1][k])
+
+
+@pytest.mark.gpu
+def test_gpu_gbdt_on_staged_row_groups_equals_host(monkeypatch):
+    """End to end on the staging-threshold input: the booster's passes (the entry-major pass reads
+    the staged waves' rows) grow the host's trees."""
+    from fraud_detection_spark_kafka_llm_amd.models import quantize as qmod
+
+    monkeypatch.setattr(qmod, "RG_BINS", 4096)
+    vc = _csr_vc_stage()
+    indptr, cols, cnt = _csr_stage_arrays()
+    has = np.zeros(indptr.size - 1, dtype=bool)
+    has[np.repeat(np.arange(indptr.size - 1), np.diff(indptr))[(cols == 3) & (cnt >= 20)]] = True
+    y = torch.from_numpy((has ^ (np.random.default_rng(2).random(has.size) < 0.1)).astype(np.float32))
+    params = GBDTParams(n_estimators=2, max_depth=3, max_bin=64)
+    host = fit_gbdt(vc, y, params, device="cpu")
+    dev = fit_gbdt(vc, y, params, device="cuda:0")
+    assert max(t.num_nodes for t in host.trees) > 3
+    _same_trees(host.trees, dev.trees)
+
+
 def test_row_groups_from_csr_beyond_64_groups():
     """Lanes hold groups l and l + 64 in the CSR build: > 64 groups give the CSC build's layout."""
     vc = _csr_vc_wide()
@@ -222,11 +342,13 @@ def test_gpu_row_groups_from_csr_beyond_64_groups():
     for dev in ("cpu", "cuda:0"):
         v = vc.to(dev)
         rg = RowGroups(quantize(v, max_bins=64, counts=v.tf_counts, scale=v.tf_scale), bins=4096)
-        ptr, ent, gb = rg.ptr.cpu().numpy(), rg.ent.cpu().numpy(), rg.gbase.cpu().numpy()
-        out.append((ptr, np.concatenate([ent[gb[g]: gb[g] + ptr[g, -1]] for g in range(rg.G)]), rg.G))
-    assert 64 < out[0][2] == out[1][2]
+        assert rg.erow is not None and rg.em_g0 < rg.G
+        out.append(_rg_runs(rg) + (rg.G,))
+    assert 64 < out[0][3] == out[1][3]
     np.testing.assert_array_equal(out[0][0], out[1][0])
     np.testing.assert_array_equal(out[0][1], out[1][1])
+    # the staged placing (1,920 entries per wave) of groups l and l + 64: the entry-major rows too
+    np.testing.assert_array_equal(out[0][2], out[1][2])
 
 
 @pytest.mark.gpu
