@@ -291,6 +291,30 @@ def test_gpu_gbdt_native_round_equals_python_levels(monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("cxx", [True, False])
+@pytest.mark.parametrize("n", [5003, 509])
+def test_gpu_gbdt_odd_row_counts_equal_host(n, cxx, monkeypatch):
+    """Row counts that are no multiple of 8, 512 or 1024 (509: less than one 512-row partition
+    wave): the tails of the one-launch prologue passes, of the counting partitions and of the leaf
+    update from the node table, which only the runner reaches, on the C++ and the Python level loop."""
+    from fraud_detection_spark_kafka_llm_amd.models import grower
+
+    monkeypatch.setattr(grower, "GBDT_CXX_LEVELS", cxx)
+    assert _booster("cuda:0", n=n) == _booster("cpu", n=n)
+
+
+@pytest.mark.gpu
+def test_gpu_rf_odd_row_count_batch_lanes_and_host_agree(monkeypatch):
+    """6001 rows (odd): the lockstep batch, the per-tree lanes and the host grow one forest."""
+    from fraud_detection_spark_kafka_llm_amd.models import forest_batch
+
+    ref = _forest("cpu", n=6001)
+    assert _forest("cuda:0", n=6001) == ref
+    monkeypatch.setattr(forest_batch, "BATCH", False)
+    assert _forest("cuda:0", n=6001) == ref
+
+
+@pytest.mark.gpu
 def test_gpu_gbdt_large_shard_paths_equal_host(monkeypatch):
     """the >4M-row regime on small data -- the list kernels' 2048-row waves, no
     partition row counts (partition_counts_ok false) and the fewest-rows sibling choice -- grows
