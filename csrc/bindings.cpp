@@ -5,6 +5,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include "contrib.h"
 #include "scoring.h"
 #include "ops.h"
 
@@ -267,6 +268,96 @@ void score_csr(const Tensor& indptr, const Tensor& idx, const Tensor& val, const
     score_csr_t<float>(indptr, idx, val, lr_w, lr_b, trees, K, cmp_less, out, threads);
   else
     score_csr_t<double>(indptr, idx, val, lr_w, lr_b, trees, K, cmp_less, out, threads);
+}
+
+// ---------------------------------------------------------------- TreeSHAP contributions
+// tables: TreePaths.tensors(device), in the order of fdx::ContribPaths
+template <class V>
+void tree_contributions_t(const Tensor& indptr, const Tensor& idx, const Tensor& val, const fdx::ContribPaths& p,
+                          const Tensor& out, const optional<std::vector<Tensor>>& scratch, int64_t threads) {
+  const auto dev = indptr.device();
+  fdx::ContribArgs<V> a{};
+  a.indptr = indptr.data_ptr<int64_t>();
+  a.idx = idx.data_ptr<int32_t>();
+  a.val = val.data_ptr<V>();
+  a.rows = indptr.numel() - 1;
+  a.p = p;
+  a.out = out.data_ptr<double>();
+  if (dev.is_cuda()) {
+    FDX_CHECK(a.rows <= fdx::kContribRowsPerTile, "more rows than one tile");
+    FDX_CHECK(scratch && scratch->size() == 3, "device scratch = (xs, masks, partials)");
+    const auto& s = *scratch;
+    for (const auto& x : s) check_dev(x, dev, "scratch");
+    const int64_t rt = fdx::kContribRowsPerTile;
+    FDX_CHECK(s[0].scalar_type() == at::kDouble && s[0].numel() >= p.U * rt, "xs scratch: float64 [U * rows_per_tile]");
+    FDX_CHECK(s[1].scalar_type() == at::kInt && s[1].numel() >= p.P * rt, "mask scratch: int32 [P * rows_per_tile]");
+    FDX_CHECK(s[2].scalar_type() == at::kDouble && s[2].numel() >= p.NB * rt,
+              "partials scratch: float64 [blocks * rows_per_tile]");
+    a.xs = s[0].data_ptr<double>();
+    a.masks = reinterpret_cast<uint32_t*>(s[1].data_ptr<int32_t>());
+    a.partials = s[2].data_ptr<double>();
+    c10::hip::HIPGuard guard(dev.index());
+    fdx::launch_tree_contributions<V>(a, stream_of(dev));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  } else {
+    fdx::tree_contributions_cpu<V>(a, (int)threads);
+  }
+}
+
+void tree_contributions(const Tensor& indptr, const Tensor& idx, const Tensor& val, const std::vector<Tensor>& tables,
+                        bool cmp_less, const Tensor& out, const optional<std::vector<Tensor>>& scratch,
+                        int64_t threads) {
+  const auto dev = indptr.device();
+  check_csr(indptr, idx, val, dev);
+  check_dev(out, dev, "out");
+  FDX_CHECK(out.scalar_type() == at::kDouble, "out must be float64");
+  FDX_CHECK(tables.size() == 13, "path tables = TreePaths.tensors()");
+  static const at::ScalarType kinds[13] = {at::kInt, at::kInt, at::kDouble, at::kInt, at::kDouble, at::kDouble, at::kDouble,
+                                           at::kInt, at::kInt, at::kInt, at::kInt, at::kInt, at::kDouble};
+  for (int i = 0; i < 13; ++i) {
+    check_dev(tables[i], dev, "path table");
+    FDX_CHECK(tables[i].scalar_type() == kinds[i], "path table dtype");
+  }
+  fdx::ContribPaths p{};
+  p.U = (int32_t)tables[0].numel();
+  p.P = (int32_t)tables[2].numel();
+  p.E = (int32_t)tables[3].numel();
+  p.NB = (int32_t)tables[11].numel();
+  FDX_CHECK(tables[1].numel() == p.P + 1, "path_ptr needs P + 1 entries");
+  for (int i : {4, 5, 6, 7, 8}) FDX_CHECK(tables[i].numel() == p.E, "element arrays size");
+  FDX_CHECK(tables[9].numel() == p.U + 1 && tables[10].numel() == p.U + 1, "slot_ptr / slot_blk need U + 1 entries");
+  FDX_CHECK(tables[12].numel() == (fdx::kContribMaxDepth + 1) * fdx::kContribMaxDepth, "shapley weight table size");
+  p.features = tables[0].data_ptr<int32_t>();
+  p.path_ptr = tables[1].data_ptr<int32_t>();
+  p.path_v = tables[2].data_ptr<double>();
+  p.pe_slot = tables[3].data_ptr<int32_t>();
+  p.pe_z = tables[4].data_ptr<double>();
+  p.pe_lo = tables[5].data_ptr<double>();
+  p.pe_hi = tables[6].data_ptr<double>();
+  p.el_path = tables[7].data_ptr<int32_t>();
+  p.el_pos = tables[8].data_ptr<int32_t>();
+  p.slot_ptr = tables[9].data_ptr<int32_t>();
+  p.slot_blk = tables[10].data_ptr<int32_t>();
+  p.blk_slot = tables[11].data_ptr<int32_t>();
+  p.shapley = tables[12].data_ptr<double>();
+  p.cmp_less = cmp_less;
+  const int64_t rows = indptr.numel() - 1;
+  FDX_CHECK(out.numel() >= rows * p.U, "out too small");
+  if (val.scalar_type() == at::kFloat)
+    tree_contributions_t<float>(indptr, idx, val, p, out, scratch, threads);
+  else
+    tree_contributions_t<double>(indptr, idx, val, p, out, scratch, threads);
+}
+
+pybind11::dict contrib_limits() {
+  pybind11::dict d;
+  d["block_elems"] = fdx::kContribBlockElems;
+  d["paths_per_chunk"] = fdx::kContribPathsPerChunk;
+  d["lds_row_cap"] = 0;   // rows are not staged in LDS: no cap on a row's entries
+  d["rows_per_group"] = fdx::kContribRowsPerGroup;
+  d["rows_per_tile"] = fdx::kContribRowsPerTile;
+  d["max_depth"] = fdx::kContribMaxDepth;
+  return d;
 }
 
 void spmv(const Tensor& indptr, const Tensor& idx, const Tensor& val, const Tensor& x, const Tensor& y,
@@ -616,6 +707,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("token_keys", &token_keys, "CountVectorizer fit: 64-bit token keys (count pass / key pass)");
   m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score");
   m.def("score_csr", &score_csr, "LR / tree-ensemble scoring of a CSR feature matrix");
+  m.def("tree_contributions", &tree_contributions, "path-dependent TreeSHAP of one row tile over a path table");
+  m.def("contrib_limits", &contrib_limits, "structural constants of the TreeSHAP kernels");
   m.def("spmv", &spmv, "y = X x (CSR, fp64 accumulate)");
   m.def("spmv_t", &spmv_t, "g += X^T r (CSR, fp64)");
   m.def("doc_freq", &doc_freq, "IDF document frequencies (device)");

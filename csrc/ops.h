@@ -41,6 +41,12 @@ template <class V> void launch_spmv_t(const int64_t* indptr, const int32_t* idx,
 template <class V> void launch_doc_freq(const int32_t* idx, const V* val, int64_t nnz, int64_t* df,
                                        hipStream_t stream);
 
+// ---------------------------------------------------------------- TreeSHAP (contrib_kernels.hip / contrib_cpu.cpp)
+template <class V> struct ContribArgs;   // contrib.h
+// one row tile (rows <= kContribRowsPerTile; xs zeroed by the caller)
+template <class V> void launch_tree_contributions(const ContribArgs<V>& a, hipStream_t stream);
+template <class V> void tree_contributions_cpu(const ContribArgs<V>& a, int threads);
+
 // ---------------------------------------------------------------- feature-major order (sort_kernels.hip)
 template <class V>
 struct FeatureOrderArgs {

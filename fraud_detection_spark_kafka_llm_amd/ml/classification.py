@@ -20,7 +20,7 @@ from ..ops.text import LinearScorer, TreeArrays
 from .base import Estimator, Model, Param, register
 from .frame import Frame
 from .linalg import DenseVector, VectorColumn
-from .tree_model import NODE_FIELDS, Tree, ensemble_arrays, feature_importances
+from .tree_model import NODE_FIELDS, Tree, ensemble_arrays, ensemble_paths, feature_importances
 
 
 class _PredictorParams:
@@ -70,6 +70,32 @@ class ClassificationModelBase(_PredictorParams, Model):
         if self.getProbabilityCol():
             frame = frame.withColumn(self.getProbabilityCol(), prob)
         return frame.withColumn(self.getPredictionCol(), pred)
+
+    def _features_column(self, features) -> VectorColumn:
+        vc = features.column(self.getFeaturesCol()) if isinstance(features, Frame) else features
+        if not isinstance(vc, VectorColumn):
+            vc = VectorColumn.from_rows(list(vc))
+        if vc.size < self.numFeatures:
+            raise ValueError(f"features have size {vc.size}, model expects {self.numFeatures}")
+        return vc
+
+    def contributions(self, features) -> VectorColumn:
+        """Per-row feature contributions to the class-1 raw score of ``features`` (a ``VectorColumn``
+        or a ``Frame`` holding ``featuresCol``): a CSR column of size ``numFeatures + 1`` whose last
+        index ``numFeatures`` is the bias; a row sums to the score. Binary models only."""
+        raise NotImplementedError
+
+    def _tree_contributions(self, features, paths, bias: float) -> VectorColumn:
+        """Tree models: every row stores the ensemble's used features (ascending), then the bias."""
+        from ..ops.sparse import tree_contributions
+
+        vc = self._features_column(features)
+        phi = tree_contributions(vc, paths)
+        n, nf, dev = phi.shape[0], self.numFeatures, phi.device
+        val = torch.cat([phi, torch.full((n, 1), bias, dtype=torch.float64, device=dev)], dim=1)
+        idx = torch.cat([torch.from_numpy(paths.features), torch.tensor([nf], dtype=torch.int32)]).to(dev)
+        indptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * val.shape[1]
+        return VectorColumn(nf + 1, indptr, idx.repeat(n), val.reshape(-1))
 
     def predict(self, features) -> float:
         vc = VectorColumn.from_rows([features], size=self.numFeatures)
@@ -163,6 +189,24 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
         pred = (prob[:, 1] > self.getThreshold()).to(torch.float64)
         return rp, prob, pred
 
+    def contributions(self, features) -> VectorColumn:
+        """Every row stores its own entries ``w_f * x_f``, then the intercept at ``numFeatures``."""
+        if self.getOrDefault("family") == "multinomial":
+            raise NotImplementedError("contributions of multinomial logistic regression are not supported")
+        vc = self._features_column(features)
+        if vc.size != self.numFeatures:
+            raise ValueError(f"features have size {vc.size}, model expects {self.numFeatures}")
+        indptr, idx, val = vc.csr()
+        dev, n, nf = indptr.device, indptr.numel() - 1, self.numFeatures
+        rows = torch.arange(n + 1, dtype=torch.int64, device=dev)
+        row_of = torch.repeat_interleave(rows[:-1], indptr[1:] - indptr[:-1], output_size=int(idx.numel()))
+        out_idx = torch.full((int(idx.numel()) + n,), nf, dtype=torch.int32, device=dev)
+        out_val = torch.full((int(idx.numel()) + n,), self.intercept, dtype=torch.float64, device=dev)
+        pos = torch.arange(int(idx.numel()), dtype=torch.int64, device=dev) + row_of
+        out_idx[pos] = idx.to(torch.int32)
+        out_val[pos] = self.scorer().weights(dev)[idx.to(torch.int64)] * val.to(torch.float64)
+        return VectorColumn(nf + 1, indptr + rows, out_idx, out_val)
+
     def postprocess_numpy(self, raw: np.ndarray):
         p = np.exp(-raw[:, 0])
         np.add(p, 1.0, out=p)
@@ -240,6 +284,18 @@ class TreeClassificationModelBase(ClassificationModelBase):
         if self._arrays is None:
             self._arrays = ensemble_arrays(self._trees, self.leaf_payload, None, cmp_less=False)
         return self._arrays
+
+    def paths(self):
+        """TreeSHAP path table of class 1, cached with (and as long as) the scorer's arrays."""
+        arrays = self.scorer()
+        cached = self.__dict__.get("_paths")
+        if cached is None or cached[0] is not arrays:
+            cached = self._paths = (arrays, ensemble_paths(self._trees, self.leaf_payload, None, cmp_less=False))
+        return cached[1]
+
+    def contributions(self, features) -> VectorColumn:
+        paths = self.paths()
+        return self._tree_contributions(features, paths, paths.bias)
 
     def postprocess(self, raw: torch.Tensor):
         prob = _normalize(raw)

@@ -8,12 +8,14 @@ pre-order with ids 0..n-1 (``DecisionTreeModelReadWrite.NodeData.build``): inter
 from __future__ import annotations
 
 from dataclasses import dataclass
+from fractions import Fraction
+from math import factorial
 from typing import Optional
 
 import numpy as np
 
 from ..io import spark_format as sf
-from ..ops.text import TreeArrays
+from ..ops.text import TreeArrays, TreePaths
 
 
 @dataclass
@@ -165,6 +167,78 @@ def ensemble_arrays(trees: list, leaf_payload: str, weights: Optional[np.ndarray
     w = np.ones(len(trees)) if weights is None else np.asarray(weights, dtype=np.float64)
     return TreeArrays(np.concatenate(feats), np.concatenate(thrs), np.concatenate(lefts), np.concatenate(rights),
                       np.concatenate(leaves), np.asarray(roots, np.int32), w, K, cmp_less)
+
+
+def shapley_weights(max_depth: int = TreePaths.MAX_DEPTH) -> np.ndarray:
+    """``w[d, k] = k! (d - k - 1)! / d!`` (fp64, correctly rounded), ``[max_depth + 1, max_depth]``."""
+    w = np.zeros((max_depth + 1, max_depth))
+    for d in range(1, max_depth + 1):
+        for k in range(d):
+            w[d, k] = float(Fraction(factorial(k) * factorial(d - k - 1), factorial(d)))
+    return w
+
+
+def ensemble_paths(trees: list, leaf_payload: str, weights: Optional[np.ndarray] = None, cmp_less: bool = False,
+                   output: Optional[int] = None) -> TreePaths:
+    """Root-to-leaf paths of an ensemble for path-dependent TreeSHAP of output column ``output``
+    (default ``K - 1``: class 1 of DT/RF, the margin of a GBDT). Payloads are normalised as in
+    ``ensemble_arrays``. The cover of a node is ``stats[:, 1]`` (sum of hessians) for ``"value"``
+    and ``stats.sum(1)`` otherwise; repeated features of a path merge into one element whose ``z``
+    is the product of ``cover(child taken) / cover(node)`` and whose tests collapse to one interval."""
+    from ..ops import native
+
+    K = 1 if leaf_payload == "value" else trees[0].stats.shape[1] if trees else 2
+    out = K - 1 if output is None else int(output)
+    if not 0 <= out < K:
+        raise ValueError(f"output {out} outside the {K} leaf columns")
+    w = np.ones(len(trees)) if weights is None else np.asarray(weights, dtype=np.float64)
+    path_v, path_len, el_feat, el_z, el_lo, el_hi = [], [], [], [], [], []
+    bias = 0.0
+    for ti, t in enumerate(trees):
+        st = t.stats.astype(np.float64)
+        if leaf_payload == "value":
+            if st.shape[1] < 2:
+                raise ValueError("GBDT nodes carry no sum of hessians (cover)")
+            cover, leaf = st[:, 1], st[:, 0]
+        else:
+            cover = st.sum(1)
+            if leaf_payload == "normalized":
+                s = cover[:, None]
+                st = np.divide(st, s, out=np.zeros_like(st), where=s != 0)
+            leaf = st[:, out]
+        # depth-first, left child first; a path's elements keep the order of first appearance
+        stack = [(int(t.root), {})]
+        while stack:
+            node, elems = stack.pop()
+            f = int(t.feature[node])
+            if f < 0:
+                if len(elems) > TreePaths.MAX_DEPTH:
+                    raise ValueError(f"a path of tree {ti} uses {len(elems)} distinct features; "
+                                     f"the limit is {TreePaths.MAX_DEPTH}")
+                v = float(w[ti]) * float(leaf[node])
+                b = v
+                for fe, (z, lo, hi) in elems.items():
+                    el_feat.append(fe), el_z.append(z), el_lo.append(lo), el_hi.append(hi)
+                    b *= z
+                bias += b
+                path_v.append(v)
+                path_len.append(len(elems))
+                continue
+            c = float(cover[node])
+            if not c > 0.0:
+                raise ValueError(f"internal node {node} of tree {ti} has cover {c}: TreeSHAP needs the node "
+                                 "covers (a booster without sum_hessian has none)")
+            thr = float(t.threshold[node])
+            z0, lo0, hi0 = elems.get(f, (1.0, -np.inf, np.inf))
+            for child, is_left in ((int(t.right[node]), False), (int(t.left[node]), True)):
+                e = dict(elems)
+                z = z0 * (float(cover[child]) / c)
+                e[f] = (z, lo0, min(hi0, thr)) if is_left else (z, max(lo0, thr), hi0)
+                stack.append((child, e))
+    features = np.unique(np.asarray(el_feat, dtype=np.int64))
+    return TreePaths(features, np.concatenate([[0], np.cumsum(path_len)]), path_v,
+                     np.searchsorted(features, np.asarray(el_feat, dtype=np.int64)), el_z, el_lo, el_hi,
+                     shapley_weights(), bias, cmp_less, out, native.lib().contrib_limits()["block_elems"])
 
 
 def feature_importances(trees: list, num_features: int, tree_weights: Optional[np.ndarray] = None) -> np.ndarray:

@@ -25,7 +25,7 @@ from ..ops.text import TreeArrays
 from .base import Estimator, Param, register
 from .classification import ClassificationModelBase
 from .frame import Frame
-from .tree_model import NODE_FIELDS, Tree, ensemble_arrays
+from .tree_model import NODE_FIELDS, Tree, ensemble_arrays, ensemble_paths
 
 
 class _XGBParams:
@@ -35,6 +35,8 @@ class _XGBParams:
                Param("probability_col", "probability column", "probability", str),
                Param("raw_prediction_col", "raw prediction column", "rawPrediction", str),
                Param("weight_col", "weight column", None, str, has_default=False),
+               Param("pred_contrib_col", "feature-contribution (TreeSHAP) output column", None, str,
+                     has_default=False),
                Param("num_workers", "data-parallel workers", 1, int),
                Param("max_depth", "max tree depth", 6, int),
                Param("n_estimators", "boosting rounds", 100, int),
@@ -139,6 +141,26 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
             # keep XGBoost's "x < split_condition" semantics
             self._arrays = ensemble_arrays(self._trees, "value", None, cmp_less=True)
         return self._arrays
+
+    def paths(self):
+        """TreeSHAP path table of the margin, cached with (and as long as) the scorer's arrays."""
+        arrays = self.scorer()
+        cached = self.__dict__.get("_paths")
+        if cached is None or cached[0] is not arrays:
+            cached = self._paths = (arrays, ensemble_paths(self._trees, "value", None, cmp_less=True))
+        return cached[1]
+
+    def contributions(self, features):
+        """Feature contributions to the margin; the bias entry includes ``base_margin``, so a row
+        sums to ``rawPrediction[:, 1]`` (xgboost's ``pred_contribs``)."""
+        paths = self.paths()
+        return self._tree_contributions(features, paths, paths.bias + self.base_margin)
+
+    def _transform(self, frame: Frame) -> Frame:
+        out = super()._transform(frame)
+        if self.isSet("pred_contrib_col"):
+            out = out.withColumn(self.getOrDefault("pred_contrib_col"), self.contributions(frame))
+        return out
 
     def postprocess(self, raw: torch.Tensor):
         m = raw[:, 0] + self.base_margin

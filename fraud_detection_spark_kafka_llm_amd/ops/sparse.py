@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import native
-from .text import LinearScorer, TreeArrays
+from .text import LinearScorer, TreeArrays, TreePaths
 
 
 def _csr(vc):
@@ -41,6 +41,44 @@ def score_csr(vc, scorer, threads: int = 0) -> torch.Tensor:
         C.score_csr(indptr, idx, val, None, 0.0, scorer.tensors(dev), scorer.K, scorer.cmp_less, out, threads)
         return out
     raise TypeError(f"unknown scorer {type(scorer)}")
+
+
+def contrib_limits() -> dict:
+    """Structural constants of the TreeSHAP kernels (block size of the summation order, paths per
+    workgroup chunk, rows per workgroup and per launch tile, depth limit)."""
+    return dict(native.lib().contrib_limits())
+
+
+def tree_contributions(vc, paths, threads: int = 0) -> torch.Tensor:
+    """Path-dependent TreeSHAP of every row: ``[N, U]`` fp64, column ``u`` = contribution of feature
+    ``paths.features[u]`` to the explained output; a row sums to its score minus ``paths.bias``.
+    Rows hold finite values with distinct indices. The device path runs in tiles of
+    ``rows_per_tile`` rows so its scratch stays bounded; device and host agree bitwise."""
+    if not isinstance(paths, TreePaths):
+        raise TypeError(f"expected TreePaths, got {type(paths)}")
+    if paths.max_feature() >= vc.size:
+        raise ValueError("tree references a feature beyond the feature space")
+    indptr, idx, val = _csr(vc)
+    dev = indptr.device
+    n = indptr.numel() - 1
+    U = int(paths.features.size)
+    out = torch.empty((n, U), dtype=torch.float64, device=dev)
+    if n == 0 or U == 0:
+        return out
+    C = native.lib()
+    tabs = paths.tensors(dev)
+    if dev.type != "cuda":
+        C.tree_contributions(indptr, idx, val, tabs, paths.cmp_less, out, None, threads)
+        return out
+    tile = int(C.contrib_limits()["rows_per_tile"])
+    xs = torch.empty(U * tile, dtype=torch.float64, device=dev)
+    masks = torch.empty(paths.num_paths * tile, dtype=torch.int32, device=dev)
+    partials = torch.empty(paths.num_blocks * tile, dtype=torch.float64, device=dev)
+    for r0 in range(0, n, tile):
+        r1 = min(n, r0 + tile)
+        xs.zero_()
+        C.tree_contributions(indptr[r0:r1 + 1], idx, val, tabs, paths.cmp_less, out[r0:r1], [xs, masks, partials], 0)
+    return out
 
 
 def spmv(indptr, idx, val, x: torch.Tensor, threads: int = 0) -> torch.Tensor:

@@ -234,6 +234,68 @@ class TreeArrays(_DeviceCached):
         return int(self.feat.max()) if self.feat.size else -1
 
 
+class TreePaths(_DeviceCached):
+    """Path table of an ensemble for TreeSHAP (see ``fdx::ContribPaths``; built by
+    ``ml.tree_model.ensemble_paths``). An *element* is one distinct feature on one root-to-leaf
+    path: its slot in ``features``, the fraction ``z`` of the cover that follows the path there and
+    the merged threshold tests as an interval ``[lo, hi]`` (``cmp_less``: ``lo <= x < hi``, else
+    ``lo < x <= hi``). Elements are stored path-major (``pe_*``) and once more sorted by
+    ``(slot, path)`` (``el_*`` with ``slot_ptr`` segments, cut into blocks of ``block_elems``):
+    that order is the summation order of both back ends."""
+
+    MAX_DEPTH = 32
+
+    def __init__(self, features, path_ptr, path_v, pe_slot, pe_z, pe_lo, pe_hi, shapley, bias: float,
+                 cmp_less: bool, output: int, block_elems: int):
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)   # noqa: E731
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)   # noqa: E731
+        self.features, self.path_ptr, self.path_v = i32(features), i32(path_ptr), f64(path_v)
+        self.pe_slot, self.pe_z, self.pe_lo, self.pe_hi = i32(pe_slot), f64(pe_z), f64(pe_lo), f64(pe_hi)
+        self.shapley = f64(shapley).reshape(-1)
+        self.bias, self.cmp_less, self.output = float(bias), bool(cmp_less), int(output)
+        self.block_elems = int(block_elems)
+        U, P, E = self.features.size, self.path_v.size, self.pe_slot.size
+        depth = np.diff(self.path_ptr)
+        if self.path_ptr.size != P + 1 or (P and (self.path_ptr[0] != 0 or self.path_ptr[-1] != E)) or np.any(depth < 0):
+            raise ValueError("inconsistent path offsets")
+        if np.any(depth > self.MAX_DEPTH):
+            raise ValueError(f"a path uses more than {self.MAX_DEPTH} distinct features")
+        if not (self.pe_z.size == self.pe_lo.size == self.pe_hi.size == E):
+            raise ValueError("inconsistent element arrays")
+        if E and (self.pe_slot.min() < 0 or self.pe_slot.max() >= U):
+            raise ValueError("element slot out of range")
+        if self.shapley.size != (self.MAX_DEPTH + 1) * self.MAX_DEPTH or self.block_elems < 1:
+            raise ValueError("bad Shapley weight table or block size")
+        # the (slot, path) order: a stable sort of the path-major elements by slot
+        el_of_path = np.repeat(np.arange(P, dtype=np.int32), depth)
+        order = np.argsort(self.pe_slot, kind="stable")
+        self.el_path = i32(el_of_path[order])
+        self.el_pos = i32((np.arange(E, dtype=np.int64) - self.path_ptr[:-1].astype(np.int64)[el_of_path])[order])
+        lens = np.bincount(self.pe_slot, minlength=U)
+        if np.any(lens == 0):
+            raise ValueError("every slot needs at least one element")
+        self.slot_ptr = i32(np.concatenate([[0], np.cumsum(lens)]))
+        nblk = (lens + self.block_elems - 1) // self.block_elems
+        self.slot_blk = i32(np.concatenate([[0], np.cumsum(nblk)]))
+        self.blk_slot = i32(np.repeat(np.arange(U), nblk))
+
+    @property
+    def num_paths(self) -> int:
+        return int(self.path_v.size)
+
+    @property
+    def num_blocks(self) -> int:
+        return int(self.blk_slot.size)
+
+    def max_feature(self) -> int:
+        return int(self.features[-1]) if self.features.size else -1
+
+    def tensors(self, device) -> list:
+        return self._cached(device, lambda d: [torch.from_numpy(a).to(d) for a in (
+            self.features, self.path_ptr, self.path_v, self.pe_slot, self.pe_z, self.pe_lo, self.pe_hi,
+            self.el_path, self.el_pos, self.slot_ptr, self.slot_blk, self.blk_slot, self.shapley)])
+
+
 # ----------------------------------------------------------------------------- results
 class FeatureResult:
     """Outputs of one fused launch. ``raw`` is ``[D, K]`` fp64 (LR: margin; trees: raw sums)."""

@@ -109,10 +109,55 @@ class ClassificationAgent:
 
         return VectorColumn(fp.dim, ip, ix, v.to(torch.float64))
 
+    def contributing_words(self, dialogue: str, n: int = 10) -> list:
+        """The words of ``dialogue`` that moved the classifier's class-1 score most: dicts with
+        ``word``, ``feature``, ``value`` (the TF-IDF value) and ``contribution`` (the model's
+        ``contributions``: TreeSHAP for tree models, ``w_f * x_f`` for logistic regression), by
+        descending ``|contribution|``, ties by feature index. Only features present in the
+        dialogue are listed. CountVectorizer features name their vocabulary word; HashingTF
+        buckets name the dialogue's own filtered tokens that hash there, joined with ``/``."""
+        from ..ml.feature import CountVectorizerModel
+        from ..ops import oracle
+
+        fp = self.fused
+        if fp.model is None:
+            raise ValueError("pipeline has no classifier stage")
+        vc = self._features([dialogue])
+        _, ix, v = vc.csr()
+        col = fp.model.contributions(vc)
+        _, cx, cv = col.csr()
+        contrib = dict(zip(cx.cpu().tolist(), cv.cpu().tolist()))
+        items = [(f, x, contrib[f]) for f, x in zip(ix.cpu().tolist(), v.cpu().tolist()) if f in contrib]
+        items.sort(key=lambda t: (-abs(t[2]), t[0]))
+        if isinstance(fp.tf, CountVectorizerModel):
+            words = {f: fp.tf.vocabulary[f] for f, _, _ in items}
+        else:
+            toks = oracle.tokenize(oracle.clean_text(dialogue))
+            if fp.stopwords is not None:
+                toks = oracle.remove_stopwords(toks, fp.stopwords)
+            buckets: dict = {}
+            for t in dict.fromkeys(toks):
+                buckets.setdefault(oracle.term_index(t, fp.dim), []).append(t)
+            words = {f: "/".join(buckets.get(f, [])) for f, _, _ in items}
+        return [{"word": words[f], "feature": int(f), "value": float(x), "contribution": float(c)}
+                for f, x, c in items[:max(0, int(n))]]
+
+    @staticmethod
+    def evidence_paragraph(evidence: Sequence[dict]) -> str:
+        listed = ", ".join(f"{e['word']!r} ({e['contribution']:+.4g})" for e in evidence)
+        return ("\n\n        **Model Evidence**:\n"
+                "        Words of this dialogue with their signed contribution to the classifier's fraud score "
+                f"(positive pushes towards fraud, negative away from it), strongest first: {listed}")
+
     def classify_and_explain(self, dialogue: str, temperature: float = 0.7, prediction: Optional[dict] = None,
-                             with_history: bool = True) -> dict:
+                             with_history: bool = True, evidence: int = 0) -> dict:
         res = prediction or self.predict_and_get_label(dialogue)
-        analysis = self.analyzer.analyze_prediction(dialogue, res["prediction"], res["confidence"], temperature)
+        words = self.contributing_words(dialogue, evidence) if evidence > 0 else None
+        if words is None:
+            analysis = self.analyzer.analyze_prediction(dialogue, res["prediction"], res["confidence"], temperature)
+        else:
+            prompt = self.analyzer.create_prompt(dialogue, res["prediction"], res["confidence"])
+            analysis = self.analyzer.llm.generate(prompt + self.evidence_paragraph(words), temperature)
         insight = None
         if with_history and self._historical is not None:
             cases = self.find_similar_historical_cases(dialogue)
@@ -123,5 +168,8 @@ class ClassificationAgent:
                     f"New Case: {dialogue}\n\n"
                     f"Historical Similar Cases:\n{cases_str}\n\n"
                     "Identify any consistent patterns or anomalies.", temperature)
-        return {"prediction": res["prediction"], "confidence": res["confidence"], "analysis": analysis,
-                "historical_insight": insight}
+        out = {"prediction": res["prediction"], "confidence": res["confidence"], "analysis": analysis,
+               "historical_insight": insight}
+        if words is not None:
+            out["evidence"] = words
+        return out
