@@ -47,6 +47,28 @@ template <class V> struct ContribArgs;   // contrib.h
 template <class V> void launch_tree_contributions(const ContribArgs<V>& a, hipStream_t stream);
 template <class V> void tree_contributions_cpu(const ContribArgs<V>& a, int threads);
 
+// ---------------------------------------------------------------- validation monitoring (eval_kernels.hip / eval_cpu.cpp)
+template <class V> struct TreeEvalArgs;   // eval.h
+struct EvalSumArgs;
+template <class V> void launch_tree_eval_update(const TreeEvalArgs<V>& a, hipStream_t stream);
+template <class V> void tree_eval_update_cpu(const TreeEvalArgs<V>& a, int threads);
+// `blocks` <= 0: sized from n (the sums are integers: any grid gives the same bits)
+void launch_eval_sums(const EvalSumArgs& a, int blocks, hipStream_t stream);
+void eval_sums_cpu(const EvalSumArgs& a, int threads);
+// (key, label byte) of every margin; sorted by key they give out = (U2, P, N)
+size_t eval_auc_temp_bytes(int64_t n);
+int64_t eval_auc_tiles(int64_t n);
+struct EvalAucScratch {
+  uint64_t* keys[2];     // [n] each
+  uint8_t* labels[2];    // [n] each
+  void* temp;            // eval_auc_temp_bytes(n)
+  size_t temp_bytes;
+  int64_t* tiles;        // [4 * eval_auc_tiles(n)]
+};
+void launch_eval_auc(const double* margin, const float* label, int64_t n, const EvalAucScratch& s, int64_t* out,
+                     hipStream_t stream);
+void eval_auc_cpu(const double* margin, const float* label, int64_t n, int64_t* out);
+
 // ---------------------------------------------------------------- feature-major order (sort_kernels.hip)
 template <class V>
 struct FeatureOrderArgs {

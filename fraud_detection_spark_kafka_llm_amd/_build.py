@@ -182,6 +182,24 @@ def build_contrib_selftest(sanitize: bool = True, out: Path | None = None) -> Pa
     return out
 
 
+def build_eval_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/eval_selftest.cpp`` + the validation-monitoring host twins (``eval_cpu.cpp``) as a
+    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
+    ``build_contrib_selftest`` (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("eval_selftest_asan" if sanitize else "eval_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "eval_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "eval_cpu.cpp"}"\n#include "{CSRC / "tests" / "eval_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -190,9 +208,12 @@ def main(argv=None) -> int:
     ap.add_argument("--host-selftest", action="store_true", help="build + run the ASan/UBSan host self-test")
     ap.add_argument("--contrib-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the TreeSHAP host twin")
+    ap.add_argument("--eval-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the validation-monitoring host twins")
     args = ap.parse_args(argv)
-    if args.host_selftest or args.contrib_selftest:
-        exe = build_host_selftest() if args.host_selftest else build_contrib_selftest()
+    if args.host_selftest or args.contrib_selftest or args.eval_selftest:
+        exe = build_host_selftest() if args.host_selftest else \
+            (build_contrib_selftest() if args.contrib_selftest else build_eval_selftest())
         return subprocess.run([str(exe)], env={**os.environ, **SELFTEST_ENV}).returncode
     path = build(force=args.force, jobs=args.jobs, verbose=args.verbose)
     print(f"built {path}")

@@ -37,6 +37,10 @@ class _XGBParams:
                Param("weight_col", "weight column", None, str, has_default=False),
                Param("pred_contrib_col", "feature-contribution (TreeSHAP) output column", None, str,
                      has_default=False),
+               Param("validation_indicator_col", "boolean column: true rows form the validation set", None, str,
+                     has_default=False),
+               Param("early_stopping_rounds", "stop after this many rounds without a better validation metric",
+                     None, int, has_default=False),
                Param("num_workers", "data-parallel workers", 1, int),
                Param("max_depth", "max tree depth", 6, int),
                Param("n_estimators", "boosting rounds", 100, int),
@@ -71,6 +75,26 @@ class _XGBParams:
         return self.getOrDefault("raw_prediction_col")
 
 
+def _as_numpy(col):
+    if isinstance(col, torch.Tensor):
+        return col.cpu().numpy()
+    return np.asarray(list(col) if not isinstance(col, np.ndarray) else col)
+
+
+def split_validation(X, y, w, mask):
+    """(validation features, labels, weights, training features, labels, weights): rows with a
+    true ``mask`` validate, the rest train; the weight column is split the same way."""
+    mask = np.asarray(mask).astype(bool)
+    vi, ti = np.nonzero(mask)[0], np.nonzero(~mask)[0]
+    yy = y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray([float(v) for v in y], dtype=np.float32))
+    ww = None if w is None else np.asarray(_as_numpy(w), dtype=np.float32)
+
+    def part(ix):
+        return X.take(ix), yy[torch.from_numpy(ix).to(yy.device)], None if ww is None else ww[ix]
+
+    return (*part(vi), *part(ti))
+
+
 @register("xgboost.spark.core.SparkXGBClassifier")
 class SparkXGBClassifier(_XGBParams, Estimator):
     _uid_prefix = "SparkXGBClassifier"
@@ -92,6 +116,19 @@ class SparkXGBClassifier(_XGBParams, Estimator):
                        deterministic=bool(self.getOrDefault("deterministic")))
         w = frame.column(self.getOrDefault("weight_col")) if self.isSet("weight_col") else None
         X, y = frame.column(self.getFeaturesCol()), frame.column(self.getLabelCol())
+        # validation rows (xgboost.spark's validation_indicator_col): split off before training, so
+        # the base score, bins and trees are those of a fit on the remaining rows alone.
+        # eval_metric is read only here
+        mask, ev = None, {}
+        if self.isSet("validation_indicator_col"):
+            from ..models.monitor import check_eval_args
+
+            mask = np.asarray(_as_numpy(frame.column(self.getOrDefault("validation_indicator_col")))).astype(bool)
+            ev = dict(eval_metric=self.getOrDefault("eval_metric"),
+                      early_stopping_rounds=self._paramMap.get("early_stopping_rounds"))
+            check_eval_args((None, None, w if mask.any() else None), ev["eval_metric"], ev["early_stopping_rounds"])
+            if not mask.any():
+                raise ValueError("the validation set is empty")
         from ..parallel import dist as D
         from ..parallel.estimator_dp import effective_workers
 
@@ -105,11 +142,21 @@ class SparkXGBClassifier(_XGBParams, Estimator):
 
             from ..parallel.estimator_dp import fit_data_parallel
 
-            (trees, nf, base, secs), self.last_dp_report = fit_data_parallel("gbdt", X, y, w, asdict(p), nw, device=dev)
+            out, self.last_dp_report = fit_data_parallel("gbdt", X, y, w, asdict(p), nw, device=dev,
+                                                         valid_mask=mask, eval_kw=ev)
+            (trees, nf, base, secs), hist = out[:4], (out[4] if len(out) > 4 else {})
         else:          # one process, or already one rank of a torchrun job
-            res = fit_gbdt(X, y, p, weights=w, device=dev)
+            if mask is not None:
+                Xv, yv, wv, X, y, w = split_validation(X, y, w, mask)
+                res = fit_gbdt(X, y, p, weights=w, device=dev, eval_set=(Xv, yv, wv), **ev)
+            else:
+                res = fit_gbdt(X, y, p, weights=w, device=dev)
             trees, nf, base, secs = res.trees, res.num_features, res.base_margin, res.train_seconds
+            hist = dict(evals_result=res.evals_result, best_iteration=res.best_iteration, best_score=res.best_score)
         m = SparkXGBClassifierModel(trees, nf, base, uid=self.uid)
+        if mask is not None:
+            m.evals_result, m.best_iteration, m.best_score = hist["evals_result"], hist["best_iteration"], \
+                hist["best_score"]
         m._paramMap.update(self._paramMap)
         m.training_seconds = secs
         return m
@@ -126,6 +173,10 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
         self.base_margin = float(base_margin)
         self._arrays: Optional[TreeArrays] = None
         self.training_seconds = 0.0
+        # validation monitoring (fit with validation_indicator_col), as xgboost names them
+        self.best_iteration: Optional[int] = None
+        self.best_score: Optional[float] = None
+        self.evals_result: dict = {}
 
     @property
     def numFeatures(self) -> int:  # noqa: N802
@@ -197,8 +248,12 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
 
     # ------------------------------------------------------------ persistence
     def _metadata_extra(self):
-        return {"numFeatures": self._num_features, "numClasses": 2, "numTrees": len(self._trees),
-                "baseMargin": self.base_margin}
+        md = {"numFeatures": self._num_features, "numClasses": 2, "numTrees": len(self._trees),
+              "baseMargin": self.base_margin}
+        if getattr(self, "best_iteration", None) is not None:
+            md.update(bestIteration=int(self.best_iteration), bestScore=float(self.best_score),
+                      evalsResult=self.evals_result)
+        return md
 
     def _save_data(self, path) -> None:
         """xgboost.spark's writer layout: ``metadata/`` (Spark DefaultParamsWriter JSON, written by
@@ -239,6 +294,9 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
             self.base_margin = float(md.get("baseMargin", 0.0))
         self._arrays = None
         self.training_seconds = 0.0
+        self.best_iteration = int(md["bestIteration"]) if "bestIteration" in md else None
+        self.best_score = float(md["bestScore"]) if "bestScore" in md else None
+        self.evals_result = md.get("evalsResult", {})
 
     def _save_data_legacy(self, path) -> None:
         """The round-1 layout (``data/`` parquet node rows + ``xgboost_model.json``), kept for tests
@@ -280,9 +338,12 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
                                "size_leaf_vector": "1"},
             })
         base_p = 1.0 / (1.0 + np.exp(-self.base_margin))
+        attrs = {}
+        if getattr(self, "best_iteration", None) is not None:       # (strings, as xgboost writes them)
+            attrs = {"best_iteration": str(int(self.best_iteration)), "best_score": repr(float(self.best_score))}
         return {
             "learner": {
-                "attributes": {},
+                "attributes": attrs,
                 "feature_names": [], "feature_types": [],
                 "gradient_booster": {"model": {"gbtree_model_param": {"num_parallel_tree": "1",
                                                                       "num_trees": str(len(trees))},

@@ -31,7 +31,7 @@ from ..ml.tree_model import Tree
 from ..ops import native
 from ..parallel.dist import Collectives
 from ..utils import tracing
-from .grower import GrowParams, PendingTree, Workspace, grow_tree
+from .grower import GrowParams, PendingTree, Workspace, device_levels_ok, grow_tree
 from .tree import prepare
 
 
@@ -61,6 +61,12 @@ class GBDTResult:
     history: list = field(default_factory=list)
     train_seconds: float = 0.0
     shape: dict = field(default_factory=dict)     # Fa, TB, nnz of this rank's quantized features
+    # validation monitoring (eval_set): {"validation": {metric: [value per round]}}, the round of
+    # the best value and that value; with early stopping ``trees`` ends at the best round
+    evals_result: dict = field(default_factory=dict)
+    best_iteration: Optional[int] = None
+    best_score: Optional[float] = None
+    deferred: bool = False       # the host tree build ran behind the next tree's root level
 
 
 def _logit(p: float) -> float:
@@ -70,13 +76,23 @@ def _logit(p: float) -> float:
 
 def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, weights=None,
              eval_fn=None, checkpoint=None, start_trees: Optional[list] = None,
-             checkpoint_dir: Optional[str] = None, checkpoint_every: int = 10, resume: bool = False) -> GBDTResult:
+             checkpoint_dir: Optional[str] = None, checkpoint_every: int = 10, resume: bool = False,
+             eval_set=None, eval_metric: str = "auc", early_stopping_rounds: Optional[int] = None) -> GBDTResult:
     """``checkpoint_dir``: write the partial ensemble every ``checkpoint_every`` trees; with
-    ``resume=True`` continue from the last checkpoint there (any world size)."""
+    ``resume=True`` continue from the last checkpoint there (any world size).
+
+    ``eval_set = (features, labels, weights | None)``: validation rows (this rank's shard under
+    data parallelism) scored after every round with ``eval_metric`` ("auc", "logloss", "error");
+    they never influence training. ``early_stopping_rounds``: stop once the metric has not
+    strictly improved for that many rounds and keep trees ``[0 .. best_iteration]`` (xgboost's
+    ``iteration_range=(0, best_iteration + 1)``). See models/monitor.py."""
     from dataclasses import asdict
 
     from ..parallel.checkpoint import EnsembleCheckpointer, data_fingerprint, maybe_fail
+    from .monitor import ValidationMonitor, check_eval_args
 
+    if eval_set is not None:
+        check_eval_args(eval_set, eval_metric, early_stopping_rounds)
     C = native.lib()
     coll = Collectives()
     t0 = time.perf_counter()
@@ -111,6 +127,14 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
     with tracing.span("gbdt.workspace"):
         ws = Workspace(Q)
     trees = list(start_trees or [])
+    mon = None
+    if eval_set is not None:
+        mon = ValidationMonitor(Q, ws, gp, coll, eval_set, eval_metric, base, params.n_estimators,
+                                early_stopping_rounds)
+        if trees:
+            if resume_state is None:
+                raise ValueError("eval_set with start_trees needs the checkpoint that holds their validation history")
+            mon.restore(resume_state, trees)
     if trees:   # resume: replay the checkpointed trees on this rank's training rows
         from ..ml.tree_model import ensemble_arrays
         from ..ops.sparse import score_csr
@@ -125,7 +149,12 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
     # the GPU (its leaf values come from the device node table, bitwise the host's)
     defer = eval_fn is None and checkpoint is None and ckpt is None
     pending = None
+    device_table = device_levels_ok(gp, w)      # (else the host level loop: no device node table)
+    stopped = mon is not None and mon.esr is not None and bool(trees) and \
+        len(trees) - 1 - mon.best_iteration >= mon.esr
     for t in range(len(trees), params.n_estimators):
+        if stopped:
+            break
         with tracing.span("gbdt.round", round=t):
             # the round's gradients: computed inside the tree's prologue (fused with the max |g|,
             # |h| pass on the device loop's native runner) from the margins and labels
@@ -134,26 +163,55 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
             if isinstance(res, PendingTree):
                 # queued first: the host-side compaction below overlaps the margin update
                 res.update_margin(margin, ws.row_node)
+                if mon is not None:
+                    # the validation margin and round t's metric, queued behind the training-margin
+                    # update on the same stream: no host round trip, the pipeline stays deferred
+                    mon.add_device_tree()
+                    mon.queue(t)
             if pending is not None:
                 trees.append(pending.result().compacted())
                 pending = None
             if isinstance(res, PendingTree):
                 pending = res
+                # round t - 1's metric is read only now, after round t is queued: its slot is
+                # ready (or nearly), so monitoring adds no synchronisation per round
+                if mon is not None and t > 0 and mon.read(t - 1):
+                    stopped = True            # (tree t is the one overshoot tree: dropped below)
                 maybe_fail(t, model="gbdt")
                 continue
             tree = res
             node_value = torch.from_numpy(np.ascontiguousarray(tree.stats[:, 0])).to(dev)
             C.tree_leaf_update(margin, ws.row_node, node_value)
+            if mon is not None:
+                # (the device node table is read before the next tree overwrites it)
+                if device_table:
+                    mon.add_device_tree()
+                else:
+                    mon.add_tree(tree)
+                mon.queue(t)
         trees.append(tree.compacted())
+        if mon is not None:
+            stopped = mon.read(t)             # (this path waits for the host tree every round anyway)
         if eval_fn is not None:
             history.append(eval_fn(t, trees, margin))
         if checkpoint is not None:
             checkpoint(t, trees, base)
         if ckpt is not None:
-            ckpt.maybe_save(len(trees), trees, base, F, params, force=len(trees) == params.n_estimators)
+            ckpt.maybe_save(len(trees), trees, base, F, params, force=len(trees) == params.n_estimators or stopped,
+                            extra=mon.state() if mon is not None else None)
         maybe_fail(t, model="gbdt")
     if pending is not None:
-        trees.append(pending.result().compacted())
+        if stopped:
+            pending.finish()                  # (its table copy is in flight: waited for, not kept)
+        else:
+            trees.append(pending.result().compacted())
+            if mon is not None:
+                mon.read(len(trees) - 1)
+    extra = {}
+    if mon is not None:
+        if mon.esr is not None:
+            trees = trees[: mon.best_iteration + 1]
+        extra = dict(evals_result=mon.evals_result(), best_iteration=mon.best_iteration, best_score=mon.best_score)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
         from .grower import dp_runner_stats
@@ -163,7 +221,7 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
                       {"Fa": Q.Fa, "TB": Q.TB, "nnz": int(Q.csc_row.numel()),
                        "hot": int(Q.hot.size) if Q.hot is not None else 0,
                        "groups": int(Q._rowgroups.G) if getattr(Q, "_rowgroups", None) is not None else 0,
-                       "sparse_frac": _sparse_frac(getattr(Q, "_rowgroups", None))})
+                       "sparse_frac": _sparse_frac(getattr(Q, "_rowgroups", None))}, deferred=bool(defer), **extra)
 
 
 def _sparse_frac(rg) -> float:

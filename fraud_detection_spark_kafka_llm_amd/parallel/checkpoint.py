@@ -2,7 +2,8 @@
 
 Ensembles are checkpointed every ``every`` trees as a Spark-layout model directory (the same
 format as the final model, so a checkpoint is also a usable model) plus ``_resume.json``:
-``{"kind", "trees_done", "base_margin", "num_features", "params", "world_size", "data_id"}``.
+``{"kind", "trees_done", "base_margin", "num_features", "params", "world_size", "data_id"}``
+(a GBDT fit with a validation set adds ``evals_result``, ``best_iteration``, ``best_score``).
 Written by rank 0 only as a complete versioned directory ``<dir>/ckpt-<trees>/``; the pointer
 file ``<dir>/LATEST`` is then replaced atomically (``os.replace``), so a process killed at any
 point (the elastic watchdog SIGKILLs survivors) leaves either the previous or the new checkpoint
@@ -168,7 +169,9 @@ class EnsembleCheckpointer:
         return list(model.trees)[: st["trees_done"]]
 
     def maybe_save(self, trees_done: int, trees: list, base_margin: float, num_features: int, params=None,
-                   force: bool = False) -> bool:
+                   force: bool = False, extra: Optional[dict] = None) -> bool:
+        """``extra``: further keys of ``_resume.json`` (GBDT validation monitoring: ``evals_result``,
+        ``best_iteration``, ``best_score``)."""
         if not force and trees_done % self.every != 0:
             return False
         if dist.rank() != 0:
@@ -190,7 +193,7 @@ class EnsembleCheckpointer:
         p = params if params is not None else self.params
         state = {"kind": self.kind, "trees_done": trees_done, "base_margin": base_margin,
                  "num_features": num_features, "world_size": dist.world_size(), "data_id": self.data_id,
-                 "params": asdict(p) if is_dataclass(p) else p}
+                 "params": asdict(p) if is_dataclass(p) else p, **(extra or {})}
         _write_durable(tmp / "_resume.json", json.dumps(state, indent=1))
         final = self.dir / name
         if final.exists():

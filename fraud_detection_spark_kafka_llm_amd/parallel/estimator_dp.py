@@ -27,8 +27,15 @@ import torch
 from .elastic import attempt, run_elastic
 
 
-def _save(tmp: Path, vc, labels, weights) -> dict:
-    """Stage the feature matrix for the ranks; returns the bytes written per array."""
+def _save(tmp: Path, vc, labels, weights, valid_mask=None, eval_kw: Optional[dict] = None) -> dict:
+    """Stage the feature matrix for the ranks; returns the bytes written per array.
+    ``valid_mask``: the validation indicator, sharded with the rows (each rank splits its own
+    shard); ``eval_kw``: the metric and the early-stopping rounds."""
+    if valid_mask is not None:
+        import json
+
+        np.save(tmp / "valid.npy", np.asarray(valid_mask).astype(np.uint8))
+        (tmp / "eval.json").write_text(json.dumps(eval_kw or {}))
     counts, scale = getattr(vc, "tf_counts", None), getattr(vc, "tf_scale", None)
     tfidf = counts is not None and scale is not None and vc.dense is None
     if tfidf:
@@ -75,6 +82,19 @@ def _load_shard(tmp: Path, rank: int, world: int):
     return vc, y, w
 
 
+def _load_eval(tmp: Path, rank: int, world: int):
+    """This rank's rows of the validation indicator and the eval settings (None: no validation)."""
+    from .dist import shard_range
+
+    if not (tmp / "valid.npy").exists():
+        return None, {}
+    import json
+
+    mask = np.load(tmp / "valid.npy", mmap_mode="r")
+    lo, hi = shard_range(mask.size, rank, world)
+    return np.array(mask[lo:hi]).astype(bool), json.loads((tmp / "eval.json").read_text())
+
+
 def _worker(rank: int, world: int, tmp: str, kind: str, kw: dict, dev_kind: str, ckpt: str, every: int):
     tmp = Path(tmp)
     vc, y, w = _load_shard(tmp, rank, world)
@@ -83,9 +103,19 @@ def _worker(rank: int, world: int, tmp: str, kind: str, kw: dict, dev_kind: str,
     if kind == "gbdt":
         from ..models.gbdt import GBDTParams, fit_gbdt
 
+        mask, ev = _load_eval(tmp, rank, world)
+        if mask is not None:
+            from ..ml.xgboost import split_validation
+
+            vv, yv, wv, vc, y, w = split_validation(vc, y, w, mask)
+            ev = dict(eval_set=(vv, yv, wv), **ev)
         res = fit_gbdt(vc, y, GBDTParams(**kw), device=device, weights=w, checkpoint_dir=ckpt,
-                       checkpoint_every=every, resume=resume)
-        return (res.trees, res.num_features, res.base_margin, res.train_seconds) if rank == 0 else None
+                       checkpoint_every=every, resume=resume, **ev)
+        out = (res.trees, res.num_features, res.base_margin, res.train_seconds)
+        if mask is not None:         # (rank 0's history: every rank computes identical bits)
+            out += (dict(evals_result=res.evals_result, best_iteration=res.best_iteration,
+                         best_score=res.best_score),)
+        return out if rank == 0 else None
     if kind == "rf":
         from ..models.tree import fit_forest
 
@@ -132,7 +162,8 @@ def effective_workers(num_workers: int, n_rows: int, device=None, nnz: int = 0, 
 
 
 def fit_data_parallel(kind: str, vc, labels, weights, kw: dict, num_workers: int, device=None,
-                      checkpoint_dir: Optional[str] = None, checkpoint_every: int = 10, min_workers: int = 1):
+                      checkpoint_dir: Optional[str] = None, checkpoint_every: int = 10, min_workers: int = 1,
+                      valid_mask=None, eval_kw: Optional[dict] = None):
     """Train ``kind`` ("gbdt" | "rf") on ``num_workers`` rank processes; returns rank 0's result
     tuple and the watchdog report (``rep.staged_bytes``: bytes staged through shared memory)."""
     use_gpu = _resolve_device(device).type == "cuda"
@@ -142,7 +173,7 @@ def fit_data_parallel(kind: str, vc, labels, weights, kw: dict, num_workers: int
     base = "/dev/shm" if os.path.isdir("/dev/shm") else None
     tmp = Path(tempfile.mkdtemp(prefix="fdx-dp-", dir=base))
     try:
-        staged = _save(tmp, vc, labels, weights)
+        staged = _save(tmp, vc, labels, weights, valid_mask, eval_kw)
         ck = checkpoint_dir or str(tmp / "checkpoint")
         rep = run_elastic(_worker, num_workers, str(tmp), kind, kw, dev_kind, ck, checkpoint_every, backend=backend,
                           min_world=min_workers)

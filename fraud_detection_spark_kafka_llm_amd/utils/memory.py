@@ -56,6 +56,9 @@ LEVEL_HIST_BYTES = 16.0     # (g, h) int64 sums per bin per node built in one le
 RF_LANE_ROW_BYTES = 27.0    # RF: per tree in flight (models/forest_batch.py lanes), its workspace:
                             # digit words, masked digits, row -> node, packed row state, slots
                             # (~0.27 GB per lane at 10M rows, profiles/r4/rf500_sweep_*.json)
+VAL_ENTRY_BYTES = 12.0      # validation CSR of a GBDT fit: int32 index + fp64 value per entry
+VAL_ROW_BYTES = 8.0 + 8.0 + 4.0 + 2 * (8.0 + 1.0) + 9.0   # row pointer, margin, label, the AUC sort's key /
+                            # label double buffers and the radix sort's temporary (~ one more buffer)
 DEFAULT_HOT_FEATURES = 145  # dense-path features (>= 10 % of rows) of the bench dialogue corpus
 DEFAULT_GROUPS = 11         # row groups of 8192 bins (bench corpus: ~90K bins over 2^18 buckets)
 DEFAULT_BUILT_NODES = 32    # nodes built in the widest level (depth 6: 2^5)
@@ -91,16 +94,28 @@ def featurize_bytes(rows: int, nnz: int, text_bytes_per_row: float = DEFAULT_BYT
 
 def training_bytes(rows: int, nnz: int, hot_features: int = DEFAULT_HOT_FEATURES, total_bins: int = 0,
                    built_nodes: int = DEFAULT_BUILT_NODES, groups: int = DEFAULT_GROUPS,
-                   sparse_frac: float = DEFAULT_SPARSE_FRAC, rf_lanes: int = 0) -> float:
+                   sparse_frac: float = DEFAULT_SPARSE_FRAC, rf_lanes: int = 0, n_val: int = 0,
+                   val_nnz: int = 0) -> float:
     """Peak bytes of training (GBDT, row-group engine) on ``rows`` rows with ``nnz`` entries.
     ``rf_lanes`` > 0: a RandomForest with that many trees in flight instead (its CSC work items
-    and a workspace per lane on top of the shared state)."""
+    and a workspace per lane on top of the shared state). ``n_val`` > 0: plus the validation set
+    of a monitored GBDT fit (``validation_bytes``)."""
     per_entry = CSR_BYTES * CSR_SLACK + ORDER_BYTES + BIN_BYTES + RG_ENTRY_BYTES + RG_EROW_BYTES * sparse_frac
     per_row = ROW_BYTES + 4.0 * row_groups_for(nnz, groups, sparse_frac) + hot_features + LEVEL_ROW_BYTES
     if rf_lanes > 0:
         per_entry += ORDER_BYTES
         per_row += RF_LANE_ROW_BYTES * rf_lanes
-    return per_entry * nnz + per_row * rows + LEVEL_HIST_BYTES * total_bins * built_nodes * 2
+    return per_entry * nnz + per_row * rows + LEVEL_HIST_BYTES * total_bins * built_nodes * 2 \
+        + validation_bytes(n_val, val_nnz)
+
+
+def validation_bytes(n_val: int, val_nnz: int = 0) -> float:
+    """Bytes a monitored GBDT fit adds for ``n_val`` validation rows with ``val_nnz`` entries (0
+    without a validation set): the raw-valued CSR, the 8 B/row margin, labels, and for ``auc``
+    the sort's key / label double buffers and the hipCUB temporary."""
+    if n_val <= 0:
+        return 0.0
+    return VAL_ENTRY_BYTES * max(int(val_nnz), 0) + VAL_ROW_BYTES * int(n_val)
 
 
 def rf_lanes_that_fit(rows: int, want: int, free_bytes: int, headroom: float = 0.5) -> int:

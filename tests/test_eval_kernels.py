@@ -1,0 +1,314 @@
+"""The validation-monitoring ops (csrc/eval.h, eval_kernels.hip, eval_cpu.cpp): the host twins
+against independent NumPy / Python-integer oracles, the device kernels against the host twins at
+the sizes where they change behaviour (``eval_limits()``), and the sanitized self-test."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from fraud_detection_spark_kafka_llm_amd import _build
+from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
+from fraud_detection_spark_kafka_llm_amd.ml.tree_model import Tree, ensemble_arrays
+from fraud_detection_spark_kafka_llm_amd.models.monitor import eval_limits
+from fraud_detection_spark_kafka_llm_amd.ops import native
+from fraud_detection_spark_kafka_llm_amd.ops.sparse import score_csr
+
+C = native.lib()
+LIM = eval_limits()
+L, R, T = LIM["wave_load"], LIM["rows_per_group"], LIM["auc_tile"]
+DEVICES = ["cpu", pytest.param("cuda:0", marks=pytest.mark.gpu)]
+
+
+def test_limits_are_exported():
+    assert set(LIM) >= {"rows_per_group", "wave_load", "auc_tile", "reduce_block"}
+    assert all(int(v) > 0 for v in LIM.values())
+
+
+# ------------------------------------------------------------------------------- oracles
+def auc_oracle(margin, y):
+    """(U2, P, N) from a tie-grouped count in Python integers; -0.0 ties with +0.0."""
+    groups = {}
+    for m, lab in zip(margin.tolist(), y.tolist()):
+        g = groups.setdefault(0.0 if m == 0.0 else m, [0, 0])
+        g[1 if lab > 0.5 else 0] += 1
+    u2 = neg_before = pos = 0
+    for key in sorted(groups):
+        rn, rp = groups[key]
+        u2 += rp * (2 * neg_before + rn)
+        neg_before += rn
+        pos += rp
+    return u2, pos, neg_before
+
+
+def run_auc(margin, y, device):
+    out = torch.zeros(3, dtype=torch.int64, device=device)
+    C.eval_auc(torch.from_numpy(margin).to(device), torch.from_numpy(y).to(device), out)
+    return tuple(int(v) for v in out.cpu().tolist())
+
+
+def run_sums(margin, y, w, k, device, blocks=0, threads=0):
+    out = torch.zeros(3, dtype=torch.int64, device=device)
+    C.eval_sums(torch.from_numpy(margin).to(device), torch.from_numpy(y).to(device),
+                None if w is None else torch.from_numpy(w).to(device), k, out, blocks, threads)
+    return tuple(int(v) for v in out.cpu().tolist())
+
+
+def sums_oracle(margin, y, w):
+    """fsum logloss terms, the exact error weight and the exact weight sum (weights are multiples
+    of 0.25, so their sums are exact in fp64)."""
+    ls, es = [], 0.0
+    for m, lab, wi in zip(margin.tolist(), y.tolist(), w.tolist()):
+        p = 1.0 / (1.0 + math.exp(-m))
+        t = -math.log(max(p, 1e-16)) if lab > 0.5 else -math.log(max(1.0 - p, 1e-16))
+        ls.append(wi * t)
+        es += wi * float((p > 0.5) != (lab > 0.5))
+    return math.fsum(ls), es, float(np.sum(w.astype(np.float64)))
+
+
+def metric_data(n, seed):
+    rng = np.random.default_rng(seed)
+    margin = rng.normal(0, 2.5, n)
+    margin[::7] = np.round(margin[::7])           # ties, some at exactly 0
+    y = (rng.random(n) < 1 / (1 + np.exp(-margin))).astype(np.float32)
+    w = (rng.integers(1, 17, n) * 0.25).astype(np.float32)      # multiples of 0.25 in [0.25, 4]
+    return margin, y, w
+
+
+# ------------------------------------------------------------------------------- metrics, host + device
+@pytest.mark.parametrize("device", DEVICES)
+def test_auc_equals_python_integer_oracle(device):
+    margin, y, _ = metric_data(3 * T + 5, 3)
+    got = run_auc(margin, y, device)
+    assert got == auc_oracle(margin, y)
+    u2, p, n = got
+    # the same value as the rank formulation with average ranks for ties
+    order = np.argsort(margin, kind="stable")
+    ranks = np.empty(len(margin))
+    sm = margin[order]
+    i = 0
+    while i < len(sm):
+        j = i
+        while j < len(sm) and sm[j] == sm[i]:
+            j += 1
+        ranks[order[i:j]] = (i + j + 1) / 2.0
+        i = j
+    auc_rank = (ranks[y > 0.5].sum() - p * (p + 1) / 2.0) / (p * n)
+    assert abs(u2 / (2.0 * p * n) - auc_rank) < 1e-12
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("weighted", [False, True])
+def test_sums_against_fsum_reference(device, weighted):
+    n = 5000
+    margin, y, w = metric_data(n, 5)
+    if not weighted:
+        w = np.ones(n, dtype=np.float32)
+    k = int(C.eval_sum_kexp(n, float(w.max())))
+    assert k == min(40, 56 - math.ceil(math.log2(n)) - math.ceil(math.log2(max(float(w.max()), 1.0))))
+    sl, se, sw = run_sums(margin, y, w if weighted else None, k, device)
+    ref_l, ref_e, ref_w = sums_oracle(margin, y, w)
+    assert sw == int(ref_w * 2 ** k) and se == int(ref_e * 2 ** k)          # error: bitwise
+    assert float(se) / float(sw) == ref_e / ref_w
+    bound = 2.0 ** -(k + 1) * n / ref_w + 1e-13
+    diff = abs(float(sl) / float(sw) - ref_l / ref_w)
+    print(f"logloss {device} weighted={weighted}: |diff| = {diff:.3e} (bound {bound:.3e})")
+    assert diff <= bound
+
+
+def test_sums_do_not_depend_on_the_thread_count():
+    margin, y, w = metric_data(20000, 6)
+    k = int(C.eval_sum_kexp(20000, 4.0))
+    assert run_sums(margin, y, w, k, "cpu", threads=1) == run_sums(margin, y, w, k, "cpu", threads=7)
+
+
+def test_sanitized_host_twin_selftest():
+    exe = _build.build_eval_selftest(sanitize=True)
+    res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode == 0, res.stdout + res.stderr
+    assert "eval selftest ok" in res.stdout
+
+
+# ------------------------------------------------------------------------------- tree_eval_update
+def full_table(depth, F, seed):
+    """A node table in the level loop's layout: a full binary tree of ``depth`` levels (root only
+    for 0), level-order numbering, random features / bins, random leaf statistics."""
+    rng = np.random.default_rng(seed)
+    M = 2 ** 7
+    nn = 2 ** (depth + 1) - 1
+    feat = np.full(M, -1, np.int32)
+    binv = np.full(M, -1, np.int32)
+    left = np.full(M, -1, np.int32)
+    right = np.full(M, -1, np.int32)
+    leaf = np.zeros(M, np.uint8)
+    nbins = 5
+    for n in range(nn):
+        if 2 * n + 2 < nn:
+            feat[n], binv[n] = rng.integers(0, F), rng.integers(0, nbins)
+            left[n], right[n] = 2 * n + 1, 2 * n + 2
+        else:
+            leaf[n] = 1
+    stats = np.zeros((M, 2), np.int64)
+    stats[:nn, 0] = rng.integers(-2 ** 30, 2 ** 30, nn)
+    stats[:nn, 1] = rng.integers(1, 2 ** 30, nn)
+    kexp = np.array([27, 24], np.int32)
+    # active feature a <-> original feature 3 a + 1; thresholds of both signs (an absent feature
+    # counts as 0.0 and must go right of a negative threshold)
+    fid_orig = (3 * np.arange(F) + 1).astype(np.int64)
+    boff = (nbins * np.arange(F + 1)).astype(np.int64)
+    thr = np.sort(rng.normal(0, 1.5, (F, nbins)), axis=1).reshape(-1)
+    table = [feat, binv, left, right, leaf, stats, kexp]
+    return table, [fid_orig, boff, thr], nn
+
+
+def host_tree(table, quant, nn, eta, lam):
+    """The ml.tree_model.Tree of a node table (what tree_from_host builds)."""
+    feat, binv, left, right, leaf, stats, kexp = table
+    fid_orig, boff, thr = quant
+    inner = (leaf[:nn] == 0) & (left[:nn] >= 0)
+    fo = np.where(inner, fid_orig[np.where(inner, feat[:nn], 0)], -1).astype(np.int32)
+    th = np.where(inner, thr[boff[np.where(inner, feat[:nn], 0)] + np.where(inner, binv[:nn], 0)], 0.0)
+    G = stats[:nn, 0].astype(np.float64) * np.ldexp(1.0, -int(kexp[0]))
+    H = stats[:nn, 1].astype(np.float64) * np.ldexp(1.0, -int(kexp[1]))
+    value = eta * (-G / (H + lam))
+    return Tree(fo, th, np.where(inner, left[:nn], -1).astype(np.int32), np.where(inner, right[:nn], -1).astype(np.int32),
+                np.stack([value, H], 1), np.zeros(nn), np.where(inner, 1.0, -1.0), np.zeros(nn, np.int64), value, 0)
+
+
+def rows_csr(lengths, num_features, seed, dtype, on_threshold=None):
+    rng = np.random.default_rng(seed)
+    ptr, idx, val = [0], [], []
+    for ln in lengths:
+        ix = np.sort(rng.choice(num_features, size=ln, replace=False)).astype(np.int32)
+        v = rng.normal(0, 1.5, ln)
+        if on_threshold is not None and ln:
+            v[rng.integers(0, ln)] = on_threshold[rng.integers(0, len(on_threshold))]
+        idx.append(ix)
+        val.append(v)
+        ptr.append(ptr[-1] + ln)
+    return (torch.tensor(ptr, dtype=torch.int64), torch.from_numpy(np.concatenate(idx) if idx else np.zeros(0, np.int32)),
+            torch.from_numpy((np.concatenate(val) if val else np.zeros(0)).astype(dtype)))
+
+
+def run_update(csr, table, quant, eta, lam, mds, device):
+    m = torch.full((csr[0].numel() - 1,), 0.25, dtype=torch.float64, device=device)
+    C.tree_eval_update(*(t.to(device) for t in csr), [torch.from_numpy(a).to(device) for a in table],
+                       [torch.from_numpy(a).to(device) for a in quant], eta, lam, mds, m, 0)
+    return m.cpu()
+
+
+UPDATE_LENGTHS = [0, 1, L - 1, L, L + 1, 2 * L + 1]
+
+
+@pytest.mark.parametrize("device", DEVICES)
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("depth", [0, 6])
+def test_tree_eval_update_equals_the_scorer(device, dtype, depth):
+    """Every row length around a wave-load, every row count around a workgroup, a root-only and a
+    full depth-6 tree, thresholds of both signs against absent features: bitwise the host twin,
+    which is bitwise the model scorer (``cmp_less=True``) of the same tree."""
+    F = 48
+    num_features = 3 * F + 8            # (a validation row may hold features no tree uses)
+    table, quant, nn = full_table(depth, F, 21 + depth)
+    tree = host_tree(table, quant, nn, 0.3, 1.0)
+    arrays = ensemble_arrays([tree], "value", cmp_less=True)
+    for rows in (1, R - 1, R, R + 1, 2 * R + len(UPDATE_LENGTHS)):      # (the last: every length at least once)
+        lengths = [UPDATE_LENGTHS[(i + rows) % len(UPDATE_LENGTHS)] for i in range(rows)]
+        csr = rows_csr(lengths, num_features, 100 + rows, dtype, on_threshold=quant[2])
+        host = run_update(csr, table, quant, 0.3, 1.0, 0.0, "cpu")
+        ref = 0.25 + score_csr(VectorColumn(num_features, csr[0], csr[1], csr[2].to(torch.float64)), arrays)[:, 0]
+        assert torch.equal(host, ref)
+        if device != "cpu":
+            assert torch.equal(run_update(csr, table, quant, 0.3, 1.0, 0.0, device), host)
+
+
+@pytest.mark.parametrize("device", DEVICES)
+def test_tree_eval_update_more_rows_than_one_sweep_of_the_grid(device):
+    """Beyond rows_per_group * max_groups rows the waves stride over the rows a second time."""
+    rows = R * LIM["max_groups"] + 3
+    table, quant, nn = full_table(3, 6, 9)
+    csr = rows_csr([(i * 7) % 5 for i in range(rows)], 3 * 6 + 8, 17, np.float32)
+    host = run_update(csr, table, quant, 0.3, 1.0, 0.0, "cpu")
+    arrays = ensemble_arrays([host_tree(table, quant, nn, 0.3, 1.0)], "value", cmp_less=True)
+    ref = 0.25 + score_csr(VectorColumn(3 * 6 + 8, csr[0], csr[1], csr[2].to(torch.float64)), arrays)[:, 0]
+    assert torch.equal(host, ref)
+    assert len(set(host.tolist())) > 4                      # the rows do reach different leaves
+    if device != "cpu":
+        assert torch.equal(run_update(csr, table, quant, 0.3, 1.0, 0.0, device), host)
+
+
+@pytest.mark.parametrize("device", DEVICES)
+def test_tree_eval_update_value_on_a_threshold_goes_right(device):
+    """x == threshold follows ``x < threshold`` (right), and max_delta_step clips the leaf."""
+    table, quant, nn = full_table(1, 2, 4)
+    f, b = int(table[0][0]), int(table[1][0])
+    thr = float(quant[2][quant[1][f] + b])
+    fo = int(quant[0][f])
+    csr = (torch.tensor([0, 1, 2, 3], dtype=torch.int64), torch.tensor([fo, fo, fo], dtype=torch.int32),
+           torch.tensor([thr, np.nextafter(thr, -np.inf), np.nextafter(thr, np.inf)], dtype=torch.float64))
+    out = run_update(csr, table, quant, 0.5, 1.0, 0.0, device) - 0.25
+    tree = host_tree(table, quant, nn, 0.5, 1.0)
+    lv, rv = tree.stats[1, 0], tree.stats[2, 0]
+    assert out.tolist() == [(0.25 + rv) - 0.25, (0.25 + lv) - 0.25, (0.25 + rv) - 0.25]
+    clipped = run_update(csr, table, quant, 0.5, 1.0, 1e-3, device) - 0.25
+    assert float(clipped.abs().max()) <= 0.5 * 1e-3 + 1e-12
+
+
+# ------------------------------------------------------------------------------- GPU: AUC and sums
+def _auc_cases():
+    rng = np.random.default_rng(12)
+    cases = {}
+    for n in (1, 2, T - 1, T, T + 1, 3 * T + 5):
+        m = rng.normal(0, 1, n)
+        cases[f"n{n}"] = (m, (rng.random(n) < 0.4).astype(np.float32))
+    n = 3 * T + 5
+    y = (rng.random(n) < 0.5).astype(np.float32)
+    cases["all_equal"] = (np.full(n, 0.75), y)
+    base = np.arange(n, dtype=np.float64)            # distinct, already sorted
+    m = base.copy()
+    m[T - 10:T] = m[T - 10]                           # a run that ends exactly on a tile boundary
+    cases["run_ends_on_boundary"] = (m, y)
+    m = base.copy()
+    m[T - 1:T + 7] = m[T - 1]                         # a run that starts one before a boundary
+    cases["run_starts_before_boundary"] = (m, y)
+    m = base.copy()
+    m[T - 3:3 * T + 2] = m[T - 3]                     # a run that covers two whole tiles
+    cases["run_covers_two_tiles"] = (m, y)
+    m = rng.permutation(np.concatenate([np.zeros(n // 2), -np.zeros(n - n // 2)]))
+    m[:5] = [-1.0, 1.0, -2.0, 2.0, 0.0]
+    cases["signed_zeros"] = (m, y)
+    return cases
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(_auc_cases()))
+def test_auc_device_equals_host_and_oracle(case):
+    m, y = _auc_cases()[case]
+    perm = np.random.default_rng(1).permutation(len(m))
+    m, y = m[perm], y[perm]
+    want = auc_oracle(m, y)
+    assert run_auc(m, y, "cpu") == want
+    assert run_auc(m, y, "cuda:0") == want
+    if case == "all_equal":
+        u2, p, n = want
+        assert u2 / (2.0 * p * n) == 0.5
+
+
+@pytest.mark.gpu
+def test_sums_device_grid_independent_and_close_to_host():
+    n = 3 * LIM["reduce_block"] + 17
+    margin, y, w = metric_data(n, 8)
+    k = int(C.eval_sum_kexp(n, float(w.max())))
+    host = run_sums(margin, y, w, k, "cpu")
+    dev1 = run_sums(margin, y, w, k, "cuda:0", blocks=1)
+    dev2 = run_sums(margin, y, w, k, "cuda:0", blocks=5)
+    dev3 = run_sums(margin, y, w, k, "cuda:0")
+    assert dev1 == dev2 == dev3                         # logloss: identical bits for any grid
+    assert dev1[1:] == host[1:]                         # error and weight sums: bitwise the host's
+    diff = abs(float(dev1[0]) / dev1[2] - float(host[0]) / host[2])
+    bound = 2 * 2.0 ** -k + 1e-13
+    print(f"logloss device vs host: |diff| = {diff:.3e} (bound {bound:.3e}, k = {k})")
+    assert diff <= bound
