@@ -318,6 +318,33 @@ class RfLevels {
     lambda_ = c["lambda_"].cast<double>();
     mcw_ = c["mcw"].cast<double>();
     seed_ = c["seed"].cast<int64_t>();
+    if (c.contains("subsample")) subsample_ = c["subsample"].cast<double>();
+    keepbits_ = get_opt(c, "keepbits");             // row subsampling: the quantisation's keep bits
+    FDX_CHECK(subsample_ == 1.0 || keepbits_.has_value(), "row subsampling needs keepbits");
+    if (keepbits_)
+      FDX_CHECK(keepbits_->scalar_type() == at::kLong && keepbits_->is_contiguous() &&
+                    keepbits_->numel() >= (get(c, "row_node").numel() + 63) / 64, "keepbits [ceil(N / 64)] int64");
+    if (c.contains("col_k")) {                    // GBDT column sampling (col_begin / col_level)
+      const auto ks = c["col_k"].cast<std::vector<int64_t>>();
+      FDX_CHECK(ks.size() == 3 && c["mode"].cast<int>() == 0, "col_k: the three stage counts, GBDT");
+      for (int j = 0; j < 3; ++j) col_k_[j] = ks[(size_t)j];
+      col_on_ = col_k_[0] > 0 || col_k_[1] > 0 || col_k_[2] > 0;
+      if (col_on_) {
+        col_tree_ = get(c, "col_tree");
+        col_level_ = get(c, "col_level");
+        col_node_ = get(c, "col_node");
+        col_tkey_ = get(c, "col_tkey");
+        col_lkeys_ = get(c, "col_lkeys");
+        col_mask_ = get_opt(c, "col_mask");           // [D, F] uint8: the tree and level stages as a byte mask
+        FDX_CHECK((col_k_[0] > 0 || col_k_[1] > 0) == col_mask_.has_value(), "col_mask with an outer stage");
+        if (col_mask_)
+          FDX_CHECK(col_mask_->scalar_type() == at::kByte && col_mask_->dim() == 2 && col_mask_->is_contiguous() &&
+                        col_mask_->size(0) >= c["max_depth"].cast<int64_t>() && col_mask_->size(1) == c["F"].cast<int64_t>(),
+                    "col_mask [D, F] uint8");
+      }
+    }
+    FDX_CHECK(subsample_ > 0.0 && subsample_ <= 1.0 && (subsample_ == 1.0 || mode_ == 0),
+              "subsample: in (0, 1], below 1 for GBDT only");
     F_ = c["F"].cast<int64_t>();
     k_ = c["k"].cast<int64_t>();
     lds_ = c["lds"].cast<bool>();
@@ -391,6 +418,8 @@ class RfLevels {
     a.np = (int32_t)np;
     a.N = N;
     a.row0 = row0;
+    a.subsample = subsample_ < 1.0 ? subsample_ : 0.0;      // (GBDT rounds: tree = the round)
+    if (keepbits_ && subsample_ < 1.0) a.keepbits = reinterpret_cast<uint64_t*>(p<int64_t>(*keepbits_));
     a.kexp_out = p<int32_t>(kexp_);
     a.rowdig = reinterpret_cast<uint32_t*>(p<int32_t>(rowdig_));
     if (dig16_ && np == 1) a.dig16 = reinterpret_cast<uint16_t*>(dig16_->data_ptr());
@@ -420,6 +449,63 @@ class RfLevels {
     }
     fdx::launch_quant(a, maxv, p<int64_t>(parts_), s);
     C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+
+  // ---- GBDT column sampling (tree.h SplitArgs col_thr): nested, exactly k features a stage.
+  // col_begin (once per tree, after the prologue) queues the tree-stage threshold and every level's
+  // stage threshold; col_level (before a level's split search) queues the node-stage thresholds of
+  // the level's open nodes and tells find() the depth. All in the level's stream, no host reads.
+  // the k-th smallest priority of each key over the features of outer_mask ([F] bytes; null: all F)
+  void col_search(const Tensor& keys, bool raw, int64_t k, int64_t tree, const uint8_t* outer_mask, int64_t pop,
+                  const Tensor& out, hipStream_t s) {
+    fdx::RfSampleArgs a{};
+    a.seed = (uint64_t)seed_;
+    a.tree = (int32_t)tree;
+    a.nodes = p<int32_t>(keys);
+    a.nnodes = (int32_t)keys.numel();
+    a.F = F_;
+    a.k = k;
+    a.thr = p<double>(out);
+    a.raw_keys = raw ? 1 : 0;
+    a.outer_mask = outer_mask;
+    a.pop = pop;
+    fdx::launch_rf_sample(a, s);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+
+  void col_mask(int64_t tree, bool with_levels, hipStream_t s) {
+    fdx::ColMaskArgs m{};
+    m.seed = (uint64_t)seed_;
+    m.tree = (int32_t)tree;
+    m.F = F_;
+    m.D = with_levels ? (int32_t)col_mask_->size(0) : 1;
+    m.thr_tree = col_k_[0] > 0 ? p<double>(col_tree_) : nullptr;
+    m.thr_level = with_levels && col_k_[1] > 0 ? p<double>(col_level_) : nullptr;
+    m.mask = p<uint8_t>(*col_mask_);
+    fdx::launch_col_mask(m, s);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  }
+
+  void col_begin(int64_t tree) {
+    if (!col_on_ || !col_mask_) return;
+    c10::hip::HIPGuard guard(dev_.index());
+    const hipStream_t s = cur_stream(dev_);
+    if (col_k_[0] > 0) col_search(col_tkey_, true, col_k_[0], tree, nullptr, F_, col_tree_, s);
+    if (col_k_[0] > 0 && col_k_[1] > 0) col_mask(tree, false, s);     // row 0 = the tree stage, for the level searches
+    if (col_k_[1] > 0)
+      col_search(col_lkeys_, true, col_k_[1], tree, col_k_[0] > 0 ? p<uint8_t>(*col_mask_) : nullptr,
+                 col_k_[0] > 0 ? col_k_[0] : F_, col_level_, s);
+    col_mask(tree, true, s);
+  }
+
+  // the node-stage thresholds of level d's open nodes (nothing without a node stage)
+  void col_level(int64_t d, const Tensor& open, int64_t tree) {
+    if (!col_on_ || col_k_[2] <= 0 || open.numel() == 0) return;
+    FDX_CHECK(open.numel() <= col_node_.numel(), "col_node too small");
+    c10::hip::HIPGuard guard(dev_.index());
+    const int64_t pop = col_k_[1] > 0 ? col_k_[1] : (col_k_[0] > 0 ? col_k_[0] : F_);
+    col_search(open, false, col_k_[2], tree, col_mask_ ? p<uint8_t>(*col_mask_) + d * F_ : nullptr, pop,
+               col_node_.narrow(0, 0, open.numel()), cur_stream(dev_));
   }
 
   ~RfLevels() {
@@ -717,11 +803,11 @@ class RfLevels {
   // a node's row; None: node i = row i), best tuples into out [nodes, 5] with features + f0.
   void split(const Tensor& hist, const Tensor& totals, const Tensor& boff, const Tensor& nbins, const Tensor& zbin,
              const Tensor& fid_orig, const Tensor& node_ids, const optional<Tensor>& feat_thr, int64_t tree, int64_t f0,
-             const Tensor& out, const optional<Tensor>& row_of, const optional<Tensor>& wide) {
+             const Tensor& out, const optional<Tensor>& row_of, const optional<Tensor>& wide, int64_t col_d) {
     c10::hip::HIPGuard guard(dev_.index());
     const hipStream_t s = cur_stream(dev_);
     const int32_t nodes = (int32_t)node_ids.numel(), Fa = (int32_t)nbins.numel();
-    if (!find(hist, totals, boff, nbins, zbin, fid_orig, node_ids, feat_thr, tree, out, row_of, wide, s)) return;
+    if (!find(hist, totals, boff, nbins, zbin, fid_orig, node_ids, feat_thr, tree, out, row_of, wide, s, col_d)) return;
     if (rec_) {
       rec_->add(kRecSplitBest, fdx::SplitBestLane{p<double>(gain_), p<int32_t>(sbin_), p<int64_t>(sleft_), nodes, Fa, f0,
                                                   p<int64_t>(out), best_partials(last_split_)});
@@ -736,7 +822,8 @@ class RfLevels {
   // search (out then holds "no candidate" tuples for every node)
   bool find(const Tensor& hist, const Tensor& totals, const Tensor& boff, const Tensor& nbins, const Tensor& zbin,
             const Tensor& fid_orig, const Tensor& node_ids, const optional<Tensor>& feat_thr, int64_t tree,
-            const Tensor& out, const optional<Tensor>& row_of, const optional<Tensor>& wide, hipStream_t s) {
+            const Tensor& out, const optional<Tensor>& row_of, const optional<Tensor>& wide, hipStream_t s,
+            int64_t col_d = -1) {
     const int32_t nodes = (int32_t)node_ids.numel(), Fa = (int32_t)nbins.numel();
     FDX_CHECK(out.numel() == 5ll * nodes && out.is_contiguous() && boff.numel() == Fa + 1, "out [nodes, 5], boff");
     FDX_CHECK(hist.dim() == 3 && hist.size(2) == 2 && (row_of || hist.size(0) >= nodes), "hist rows");
@@ -776,6 +863,10 @@ class RfLevels {
     a.lambda_ = lambda_;
     a.min_child_weight = mcw_;
     a.feat_thr = p<double>(feat_thr);
+    if (col_on_ && col_d >= 0) {             // GBDT column sampling at depth col_d (col_level queued the node stage)
+      if (col_mask_) a.col_mask = p<uint8_t>(*col_mask_) + col_d * F_;
+      if (col_k_[2] > 0 && !feat_thr) a.feat_thr = p<double>(col_node_);
+    }
     a.seed = (uint64_t)seed_;
     a.tree = (int32_t)tree;
     if (fmix_ && feat_thr) a.fmix = reinterpret_cast<const uint64_t*>(p<int64_t>(*fmix_));
@@ -919,7 +1010,7 @@ class RfLevels {
     const int64_t* root = d == 0 ? root_pending_ : nullptr;
     root_pending_ = nullptr;
     find_root_ = root;
-    const bool any = find(hist, totals, boff, nbins_, zbin_, fid_orig_, open, feat_thr, tree, out, c10::nullopt, wide, s);
+    const bool any = find(hist, totals, boff, nbins_, zbin_, fid_orig_, open, feat_thr, tree, out, c10::nullopt, wide, s, d);
     find_root_ = nullptr;
     find_prev_ = nullptr;
     fdx::LevelPlanArgs a = plan_args(d, n_open, out, open, n_open_ptr, next_open, next_totals);
@@ -1149,6 +1240,8 @@ class RfLevels {
       l.nslots = n_build;
       l.wave_count = l.slot_count + 2 * n_build;
       l.counted = g_counted_ ? 1 : 0;
+      if (subsample_ < 1.0)                       // only the kept rows are listed (their own pass 0)
+        l.keepbits = reinterpret_cast<const uint64_t*>(p<int64_t>(*keepbits_));
       l.masked = em ? reinterpret_cast<uint32_t*>(p<int32_t>(*g_emdig_)) : nullptr;
       if (nc_base_ != nullptr) {                  // (the last partition's counts per node)
         l.node_counts = p<int32_t>(g_node_counts_);
@@ -1181,6 +1274,7 @@ class RfLevels {
     C10_HIP_KERNEL_LAUNCH_CHECK();
     const Tensor n_open_ptr = d == 0 ? g_one_ : st_["counts"].select(0, d - 1).narrow(0, 1, 1);
     const Tensor open = g_open_[cur].narrow(0, 0, n_open);
+    col_level(d, open, tree);
     if (!dp_) {
       const optional<Tensor> prev = d == 0 ? optional<Tensor>() : optional<Tensor>(g_hist_[nxt]);
       split_plan(d, n_open, g_hist_[cur].narrow(0, 0, n_open),
@@ -1202,7 +1296,7 @@ class RfLevels {
       // (the root's totals: the reduced totals row)
       const Tensor totals = d == 0 ? out.select(0, R - 1).narrow(0, 0, 1) : g_totals_[cur].narrow(0, 0, n_open);
       const bool any = find(out, totals, dp_boff_, dp_nbins_, dp_zbin_, dp_fid_, open, c10::nullopt, tree, ag_in,
-                            d > 0 ? optional<Tensor>(dp_row_of_[cur]) : c10::nullopt, dp_wide_, s);
+                            d > 0 ? optional<Tensor>(dp_row_of_[cur]) : c10::nullopt, dp_wide_, s, d);
       find_prev_ = nullptr;
       find_sub_par_ = find_sub_sib_ = nullptr;
       if (any)
@@ -1294,6 +1388,11 @@ class RfLevels {
   int mode_ = 1, max_depth_ = 5, wps_ = 256;
   double min_gain_ = 0.0, lambda_ = 1.0, mcw_ = 1.0;
   int64_t seed_ = 0, F_ = 1, k_ = 1;
+  double subsample_ = 1.0;
+  bool col_on_ = false;                          // GBDT column sampling: stage counts (0: stage skipped),
+  int64_t col_k_[3] = {0, 0, 0};                 //   thresholds, pseudo-node keys, optional byte mask / scratch
+  Tensor col_tree_, col_level_, col_node_, col_tkey_, col_lkeys_;
+  optional<Tensor> col_mask_, keepbits_;
   bool lds_ = true;
   at::Device dev_{at::kCPU};
   // GBDT level loop (gbdt_setup)
@@ -1717,7 +1816,7 @@ class RfBatch {
             compact_ ? ln.view(7, cur, 0, [&] { return ln.sh_local[cur].narrow(0, f0_, Fa_s_ + 1); }) : sh_boff_;
         ln.r->split(out.narrow(0, ln.row0, ln.n_build), totals, split_boff, sh_nbins_, sh_zbin_, sh_fid_, open,
                     ln.view(8, cur, ln.n_open, [&] { return ln.thr[cur].narrow(0, 0, ln.n_open); }), ln.tree, f0_,
-                    ag_in.narrow(0, ln.l0, ln.n_open), c10::nullopt, wide_);
+                    ag_in.narrow(0, ln.l0, ln.n_open), c10::nullopt, wide_, -1);
       }
     }
     const int64_t m_split = mark();
@@ -1974,6 +2073,8 @@ void register_level_ops(pybind11::module& m) {
       .def("partition", &RfLevels::partition)
       .def("split_plan", &RfLevels::split_plan)
       .def("prologue", &RfLevels::prologue)
+      .def("col_begin", &RfLevels::col_begin)
+      .def("col_level", &RfLevels::col_level)
       .def("leaf_update", &RfLevels::leaf_update)
       .def("gbdt_setup", &RfLevels::gbdt_setup)
       .def("gbdt_root", &RfLevels::gbdt_root)

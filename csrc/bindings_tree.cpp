@@ -84,7 +84,7 @@ void quant_max(const optional<Tensor>& g, const optional<Tensor>& h, const optio
 void quant(const optional<Tensor>& g, const optional<Tensor>& h, const optional<Tensor>& label,
            const optional<Tensor>& weight, int64_t seed, int64_t tree, bool bootstrap, int64_t mode, int64_t np,
            const optional<Tensor>& max_abs, const Tensor& rowdig, const Tensor& kexp, const Tensor& totals,
-           const optional<Tensor>& digp, int64_t row0) {
+           const optional<Tensor>& digp, int64_t row0, double subsample, const optional<Tensor>& keepbits) {
   const auto dev = rowdig.device();
   chk(rowdig, dev, at::kInt, "rowdig");
   chk(kexp, dev, at::kInt, "kexp");
@@ -94,9 +94,18 @@ void quant(const optional<Tensor>& g, const optional<Tensor>& h, const optional<
   FDX_CHECK(np == 1 || np == 4, "np must be 1 or 4");
   if (max_abs) { chk(*max_abs, dev, at::kDouble, "max_abs"); FDX_CHECK(max_abs->numel() == 2, "max_abs size"); }
   FDX_CHECK(np == 4 || !max_abs, "np == 1 is for integer counts (exponent 0, no max_abs)");
+  FDX_CHECK(subsample > 0.0 && subsample <= 1.0, "subsample must be in (0, 1]");
+  FDX_CHECK(subsample == 1.0 || mode == 0, "row subsampling: GBDT statistics only");
   fdx::QuantArgs a = quant_args(g, h, label, weight, seed, tree, bootstrap, mode, dev, rowdig.size(0));
   a.np = (int32_t)np;
   a.row0 = row0;
+  a.subsample = subsample < 1.0 ? subsample : 0.0;
+  if (keepbits && keepbits->defined()) {
+    chk(*keepbits, dev, at::kLong, "keepbits");
+    FDX_CHECK(keepbits->numel() >= (rowdig.size(0) + 63) / 64 && keepbits->is_contiguous() && mode == 0,
+              "keepbits [ceil(N / 64)] int64, GBDT");
+    a.keepbits = reinterpret_cast<uint64_t*>(keepbits->data_ptr<int64_t>());
+  }
   a.kexp_out = kexp.data_ptr<int32_t>();
   a.rowdig = reinterpret_cast<uint32_t*>(rowdig.data_ptr<int32_t>());
   a.totals = totals.data_ptr<int64_t>();
@@ -205,6 +214,76 @@ void rf_sample(int64_t seed, int64_t tree, const Tensor& nodes, int64_t F, int64
     C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     fdx::rf_sample_cpu(a);
+  }
+}
+
+// GBDT column sampling: out[i] = the k-th smallest priority(seed, tree, keys[i], f) over the feature
+// indices f in [0, F) with outer_mask[f] != 0 (None: all of them); exact (tree.h RfSampleArgs
+// outer_mask). pop: how many pass the mask (0: unknown). raw: keys are taken as they stand (the
+// pseudo-node keys of the tree and level stages); else a negative key is padding (out -1).
+// k >= F: every feature, out = 1.0.
+void col_thresholds(int64_t seed, int64_t tree, const Tensor& keys, bool raw, int64_t F, int64_t k, const Tensor& out,
+                    const optional<Tensor>& outer_mask, int64_t pop) {
+  const auto dev = out.device();
+  chk(keys, dev, at::kInt, "keys");
+  chk(out, dev, at::kDouble, "out");
+  FDX_CHECK(out.numel() == keys.numel() && out.is_contiguous(), "out [n]");
+  FDX_CHECK(k >= 1 && F >= 1 && pop >= 0 && pop <= F, "k, F >= 1, pop in [0, F]");
+  if (k >= F) { out.fill_(1.0); return; }
+  fdx::RfSampleArgs a{};
+  a.seed = (uint64_t)seed;
+  a.tree = (int32_t)tree;
+  a.nodes = keys.data_ptr<int32_t>();
+  a.nnodes = (int32_t)keys.numel();
+  a.F = F;
+  a.k = k;
+  a.thr = out.data_ptr<double>();
+  a.raw_keys = raw ? 1 : 0;
+  a.pop = pop;
+  if (outer_mask && outer_mask->defined()) {
+    chk(*outer_mask, dev, at::kByte, "outer_mask");
+    FDX_CHECK(outer_mask->numel() == F && outer_mask->is_contiguous(), "outer_mask [F]");
+    a.outer_mask = outer_mask->data_ptr<uint8_t>();
+  }
+  if (a.nnodes == 0) return;
+  if (dev.is_cuda()) {
+    c10::hip::HIPGuard guard(dev.index());
+    fdx::launch_rf_sample(a, stream(dev));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  } else {
+    fdx::rf_sample_cpu(a);
+  }
+}
+
+// GBDT column sampling: mask [D, F] uint8 = feature index f passes the tree stage (thr_tree [1] or
+// None: skipped) and level d's stage (thr_level [D] or None) -- tree.h ColMaskArgs.
+void col_mask(int64_t seed, int64_t tree, const optional<Tensor>& thr_tree, const optional<Tensor>& thr_level,
+              const Tensor& mask) {
+  const auto dev = mask.device();
+  chk(mask, dev, at::kByte, "mask");
+  FDX_CHECK(mask.dim() == 2 && mask.is_contiguous(), "mask [D, F] (D = 1 with thr_level None: the tree stage alone)");
+  fdx::ColMaskArgs a{};
+  a.seed = (uint64_t)seed;
+  a.tree = (int32_t)tree;
+  a.D = (int32_t)mask.size(0);
+  a.F = mask.size(1);
+  if (thr_tree && thr_tree->defined()) {
+    chk(*thr_tree, dev, at::kDouble, "thr_tree");
+    FDX_CHECK(thr_tree->numel() >= 1, "thr_tree [1]");
+    a.thr_tree = thr_tree->data_ptr<double>();
+  }
+  if (thr_level && thr_level->defined()) {
+    chk(*thr_level, dev, at::kDouble, "thr_level");
+    FDX_CHECK(thr_level->numel() >= a.D && thr_level->is_contiguous(), "thr_level [D]");
+    a.thr_level = thr_level->data_ptr<double>();
+  }
+  a.mask = mask.data_ptr<uint8_t>();
+  if (dev.is_cuda()) {
+    c10::hip::HIPGuard guard(dev.index());
+    fdx::launch_col_mask(a, stream(dev));
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  } else {
+    fdx::col_mask_cpu(a);
   }
 }
 
@@ -599,7 +678,7 @@ void rg_build_csr(const Tensor& indptr, const Tensor& idx, const Tensor& counts,
 void rg_list(const optional<Tensor>& row_node, const optional<Tensor>& node_slot, const optional<Tensor>& slot8,
              int64_t N, int64_t nslots, const Tensor& work, const Tensor& slot_start, const Tensor& list,
              const optional<Tensor>& rowdig, const optional<Tensor>& listdig, const optional<Tensor>& masked,
-             bool counted) {
+             bool counted, const optional<Tensor>& keepbits) {
   const auto dev = list.device();
   chk(work, dev, at::kInt, "work");
   chk(slot_start, dev, at::kInt, "slot_start");
@@ -626,6 +705,11 @@ void rg_list(const optional<Tensor>& row_node, const optional<Tensor>& node_slot
   a.N = N;
   a.nslots = (int32_t)nslots;
   a.counted = counted ? 1 : 0;        // (the partition's row pass wrote pass 0's counts)
+  if (keepbits && keepbits->defined()) {   // only the rows the round keeps (tree.h RgListArgs)
+    chk(*keepbits, dev, at::kLong, "keepbits");
+    FDX_CHECK(keepbits->numel() >= (N + 63) / 64 && keepbits->is_contiguous(), "keepbits [ceil(N / 64)] int64");
+    a.keepbits = reinterpret_cast<const uint64_t*>(keepbits->data_ptr<int64_t>());
+  }
   a.slot_count = work.data_ptr<int32_t>();
   a.wave_count = a.slot_count + 2 * nslots;
   a.slot_start = slot_start.data_ptr<int32_t>();
@@ -895,7 +979,8 @@ void split_find(const Tensor& hist, const Tensor& totals, const Tensor& boff, co
                 const Tensor& fid_orig, const Tensor& node_ids, const Tensor& kexp, int64_t mode, double lambda_,
                 double mcw, const optional<Tensor>& feat_thr, int64_t seed, int64_t tree, const Tensor& out_gain,
                 const Tensor& out_bin, const Tensor& out_left, const optional<Tensor>& node_tree,
-                const optional<Tensor>& wide, const optional<Tensor>& row_of) {
+                const optional<Tensor>& wide, const optional<Tensor>& row_of,
+                const optional<Tensor>& col_mask) {
   const auto dev = hist.device();
   chk(hist, dev, at::kLong, "hist");
   chk(totals, dev, at::kLong, "totals");
@@ -958,6 +1043,12 @@ void split_find(const Tensor& hist, const Tensor& totals, const Tensor& boff, co
     chk(*wide, dev, at::kInt, "wide");
     a.wide = wide->data_ptr<int32_t>();
     a.n_wide = (int32_t)wide->numel();
+  }
+  // GBDT column sampling: this level's byte mask over the original feature indices
+  if (col_mask && col_mask->defined()) {
+    chk(*col_mask, dev, at::kByte, "col_mask");
+    FDX_CHECK(col_mask->is_contiguous(), "col_mask [F]");
+    a.col_mask = col_mask->data_ptr<uint8_t>();
   }
   if (dev.is_cuda()) {
     c10::hip::HIPGuard guard(dev.index());
@@ -1271,7 +1362,10 @@ void leaf_update(const Tensor& margin, const Tensor& row_node, const Tensor& nod
 void register_tree_ops(pybind11::module& m) {
   namespace py = pybind11;
   m.def("tree_quant_max", &quant_max);
-  m.def("tree_quant", &quant);
+  m.def("tree_quant", &quant, py::arg("g"), py::arg("h"), py::arg("label"), py::arg("weight"), py::arg("seed"),
+        py::arg("tree"), py::arg("bootstrap"), py::arg("mode"), py::arg("np"), py::arg("max_abs"), py::arg("rowdig"),
+        py::arg("kexp"), py::arg("totals"), py::arg("digp"), py::arg("row0"), py::arg("subsample") = 1.0,
+        py::arg("keepbits") = py::none());
   m.def("tree_slot8", &slot8);
   m.def("tree_level_plan", &level_plan);
   m.def("tree_level_rows", &level_rows);
@@ -1289,7 +1383,8 @@ void register_tree_ops(pybind11::module& m) {
   m.def("tree_rg_build", &rg_build);
   m.def("tree_rg_list", &rg_list, py::arg("row_node"), py::arg("node_slot"), py::arg("slot8"), py::arg("N"),
         py::arg("nslots"), py::arg("work"), py::arg("slot_start"), py::arg("list"), py::arg("rowdig"),
-        py::arg("listdig"), py::arg("masked") = py::none(), py::arg("counted") = false);
+        py::arg("listdig"), py::arg("masked") = py::none(), py::arg("counted") = false,
+        py::arg("keepbits") = py::none());
   m.def("tree_rg_build_csr", &rg_build_csr, py::arg("indptr"), py::arg("idx"), py::arg("counts"), py::arg("remap"),
         py::arg("max_bin"), py::arg("fgroup"), py::arg("flocal"), py::arg("ptr"), py::arg("gbase"), py::arg("ent"),
         py::arg("work"), py::arg("erow") = py::none(), py::arg("em_g0") = 0, py::arg("ebase") = 0);
@@ -1321,7 +1416,10 @@ void register_tree_ops(pybind11::module& m) {
         py::arg("zbin"), py::arg("fid_orig"), py::arg("node_ids"), py::arg("kexp"), py::arg("mode"),
         py::arg("lambda_"), py::arg("mcw"), py::arg("feat_thr"), py::arg("seed"), py::arg("tree"),
         py::arg("out_gain"), py::arg("out_bin"), py::arg("out_left"), py::arg("node_tree"),
-        py::arg("wide") = py::none(), py::arg("row_of") = py::none());
+        py::arg("wide") = py::none(), py::arg("row_of") = py::none(), py::arg("col_mask") = py::none());
+  m.def("tree_col_thresholds", &col_thresholds, py::arg("seed"), py::arg("tree"), py::arg("keys"), py::arg("raw"),
+        py::arg("F"), py::arg("k"), py::arg("out"), py::arg("outer_mask") = py::none(), py::arg("pop") = 0);
+  m.def("tree_col_mask", &col_mask);
   m.def("tree_partition", &partition);
   m.def("tree_logistic_grad", &logistic_grad);
   m.def("tree_leaf_update", &leaf_update);

@@ -124,6 +124,9 @@ struct LevelRowsArgs;
 struct RfSampleArgs;
 void launch_rf_sample(const RfSampleArgs& a, hipStream_t s);
 void rf_sample_cpu(const RfSampleArgs& a);
+struct ColMaskArgs;
+void launch_col_mask(const ColMaskArgs& a, hipStream_t s);
+void col_mask_cpu(const ColMaskArgs& a);
 struct RfCompactArgs;
 void launch_rf_compact(const RfCompactArgs& a, hipStream_t s);
 // partials: the SplitArgs of the split search whose per-workgroup partials (part_gain) replace

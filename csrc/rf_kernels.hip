@@ -70,7 +70,7 @@ __device__ void rf_threshold_node(const RfSampleArgs& a, int bi, const unsigned 
 
   const int node = a.nodes[bi];
   const int tid = threadIdx.x;
-  if (node < 0) {                                 // padding: samples nothing
+  if (node < 0 && !a.raw_keys) {                  // padding: samples nothing
     if (tid == 0) a.thr[bi] = -1.0;
     return;
   }
@@ -105,7 +105,7 @@ __device__ void rf_threshold_node(const RfSampleArgs& a, int bi, const unsigned 
     s_prefix = 0;
     s_known = 0;
     s_k = a.k;                // 1-based rank of the wanted priority among those matching the prefix
-    s_count = a.F;
+    s_count = a.pop > 0 ? a.pop : a.F;      // (an upper bound of the searched features)
   }
   __syncthreads();
   // radix passes until the wanted bucket is small enough to rank in LDS
@@ -117,6 +117,7 @@ __device__ void rf_threshold_node(const RfSampleArgs& a, int bi, const unsigned 
     for (int i = tid; i < kBuckets; i += kThreads) s_hist[i] = 0;
     __syncthreads();
     for (int64_t f = tid; f < a.F; f += kThreads) {
+      if (!rf_outer_pass(a, f)) continue;
       const uint64_t u = rf_priority(a, rf_tree_of(a, bi), node, f);
       if (known == 0 || (u >> (53 - known)) == prefix)
         atomicAdd(&s_hist[(u >> shift) & ((1u << nbits) - 1)], 1u);
@@ -142,6 +143,7 @@ __device__ void rf_threshold_node(const RfSampleArgs& a, int bi, const unsigned 
   const int known = s_known;
   const uint64_t prefix = s_prefix;
   for (int64_t f = tid; f < a.F; f += kThreads) {
+    if (!rf_outer_pass(a, f)) continue;
     const uint64_t u = rf_priority(a, rf_tree_of(a, bi), node, f);
     if (known == 0 || (u >> (53 - known)) == prefix) {
       const uint32_t i = atomicAdd(&s_ncand, 1u);
@@ -355,6 +357,18 @@ __global__ __launch_bounds__(kChunkThreads) void rf_compact_chunks_lanes_kernel(
 }
 }  // namespace
 
+namespace {
+__global__ __launch_bounds__(kThreads) void col_mask_kernel(ColMaskArgs a) {
+  const int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (f < a.F) a.mask[(int64_t)blockIdx.y * a.F + f] = col_mask_at(a, (int)blockIdx.y, f);
+}
+}  // namespace
+
+void launch_col_mask(const ColMaskArgs& a, hipStream_t s) {
+  if (a.F <= 0 || a.D <= 0) return;
+  hipLaunchKernelGGL(col_mask_kernel, dim3((unsigned)((a.F + kThreads - 1) / kThreads), (unsigned)a.D), dim3(kThreads), 0, s, a);
+}
+
 int64_t rf_compact_chunks(int64_t max_shard_features) { return (max_shard_features + kChunkFeat - 1) / kChunkFeat; }
 
 void launch_rf_compact(const RfCompactArgs& a, hipStream_t s) {
@@ -370,7 +384,10 @@ void launch_rf_compact(const RfCompactArgs& a, hipStream_t s) {
 void launch_rf_sample(const RfSampleArgs& a, hipStream_t s) {
   // k >= F (every feature) is handled by the caller: thresholds 1.0, mask all ones
   if (a.nnodes <= 0 || a.k >= a.F) return;
-  if (a.scratch != nullptr) {
+  // (filtered or raw-key searches -- GBDT column sampling -- take the exact radix search: with k a
+  // large share of the searched features the +-8 sigma window holds more than the 2048 candidates
+  // that are ranked in LDS, so the window pass only added its own time: profiles/r10/stochastic.md)
+  if (a.scratch != nullptr && a.outer_mask == nullptr && !a.raw_keys) {
     // window [lo, hi] of expected counts k -+ (8 sqrt(k) + 8), as 53-bit priorities
     const double sd = 8.0 * sqrt((double)a.k) + 8.0;
     const double lo = fmax(0.0, (double)a.k - sd) / (double)a.F, hi = fmin((double)a.F, (double)a.k + sd) / (double)a.F;

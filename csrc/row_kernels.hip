@@ -950,6 +950,13 @@ void launch_rg_list(const RgListArgs& a0, hipStream_t s) {
   const int64_t waves = (a.N + a.list_rows - 1) / a.list_rows;   // 4 per block
   const int64_t blocks = (waves + 3) / 4;
   if (blocks <= 0) return;
+  // (the partition counted every row: pass 0 counts the kept ones. At 1M rows that pass costs
+  // subsample = 0.8 its gain, 0.975 against 0.974 ms a tree; at 10M rows the shorter lists win,
+  // 4.23 / 3.74 against 4.31 ms at 0.8 / 0.5: profiles/r10/stochastic.md)
+  if (a.keepbits != nullptr) {
+    a.counted = 0;
+    a.node_counts = nullptr;
+  }
   if (a.node_counts != nullptr && (a.row_node == nullptr || a.list_rows % kPartWaveRows != 0)) a.node_counts = nullptr;
   if (!a.counted && a.node_counts == nullptr) hipLaunchKernelGGL(rg_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, 0);
   hipLaunchKernelGGL(rg_list_scan_kernel, dim3((unsigned)a.nslots), dim3(1024), 0, s, a, waves);

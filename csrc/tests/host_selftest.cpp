@@ -313,6 +313,21 @@ static void test_rowgroups() {
   std::fill(hist.begin(), hist.end(), 0);
   run(list.data(), slot_start.data(), listdig.data(), nullptr, hist);   // (row lists for both groups)
   EXPECT(hist == ref_of({1, 3, 4, 5}));
+  // row subsampling: the list holds the built rows the round keeps, in order, and nothing else
+  uint64_t keepbits = 0;
+  for (int r = 0; r < N; ++r)
+    if (hash_uniform(11, 3, (uint64_t)(1000 + r)) < 0.5) keepbits |= 1ull << r;
+  la.keepbits = &keepbits;
+  std::fill(list.begin(), list.end(), -7);
+  rg_list_cpu(la);
+  std::vector<int32_t> kept;
+  for (int r = 0; r < N; ++r)
+    if (row_node[r] == 1 && ((keepbits >> r) & 1ull)) kept.push_back(r);
+  EXPECT(slot_start[0] == 0 && slot_start[1] == (int32_t)kept.size());
+  for (size_t i = 0; i < kept.size(); ++i) {
+    EXPECT(list[i] == kept[i] && listdig[2 * i] == rd[2 * kept[i]] && listdig[2 * i + 1] == rd[2 * kept[i] + 1]);
+  }
+  for (size_t i = kept.size(); i < (size_t)N; ++i) EXPECT(list[i] == -7);
 }
 
 int main() {

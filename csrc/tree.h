@@ -99,6 +99,14 @@ struct QuantArgs {
   const unsigned long long* max_parts;
   int64_t* zero;              // optional: [zero_n] int64 zeroed on the way (the root histogram)
   int64_t zero_n;
+  // GBDT row subsampling (mode 0): in (0, 1) the row with global index row0 + r is kept iff
+  // hash_uniform(seed, tree, row0 + r) < subsample (tree = the boosting round), and a row that is
+  // not kept has both statistics zero; 0 (the zero-initialised struct) or >= 1: every row kept.
+  // The exponents still come from the max over every row (quant_max / grad_max never mask).
+  double subsample;
+  // optional (with subsample): [ceil(N / 64)] words, bit r & 63 of word r >> 6 = row r is kept (a
+  // ballot per 64 rows, stored by one lane), for the row lists (RgListArgs keepbits)
+  uint64_t* keepbits;
 };
 constexpr int kRootSlots = 32;
 constexpr int kRootStride = 16;           // int64 words per slot (one 128-byte line)
@@ -277,10 +285,16 @@ struct RgListArgs {
   // a list wave's 512-row waves for its slot's node, and pass 0 is skipped
   const int32_t* node_counts;
   const int32_t* nc_base;
+  // GBDT row subsampling: the quantisation's keep bits (QuantArgs keepbits). With them only the
+  // rows the round keeps are listed -- the digit words of the others are zero, so they add nothing
+  // to any histogram. The partition's counts cover every row, so the list then counts its own rows
+  // (pass 0; launch_rg_list drops counted / node_counts). nullptr: every row of the built nodes.
+  const uint64_t* keepbits;
 };
 constexpr int32_t kPartWaveRows = 512;   // rows of one partition wave (64 lanes x 8 rows)
 
 FDX_HD uint32_t rg_slot_of(const RgListArgs& a, int64_t r) {
+  if (a.keepbits && !((a.keepbits[r >> 6] >> (r & 63)) & 1ull)) return 0xffu;
   if (!a.row_node) return a.slot8[r];
   const int32_t n = a.row_node[r];
   const int32_t s = (n >= 0 && n < a.num_nodes) ? a.node_slot[n] : -1;
@@ -424,6 +438,26 @@ struct RfSampleArgs {
   uint32_t* fused_counts;
   int32_t fused_cap;
   const uint64_t* fmix;           // optional [F]: mix64(f) (feature_priority_u53_pre)
+  // GBDT column sampling (nested stages, exact path only: scratch stays null). raw_keys: nodes[i]
+  // is a 32-bit key taken as it stands (the pseudo-node keys of the tree and level stages are
+  // negative as int32), never padding. outer_mask: the k-th smallest is taken over the feature
+  // indices f with outer_mask[f] != 0 (ColMaskArgs: f passes the stages before this one). pop: how
+  // many those are (0: unknown, F): a search over <= 2048 of them skips the radix pass.
+  int32_t raw_keys;
+  const uint8_t* outer_mask;
+  int64_t pop;
+};
+
+// GBDT column sampling: mask[d * F + f] = feature index f passes the tree stage and level d's stage
+// (a stage whose threshold pointer is null is skipped), once per tree for every depth.
+struct ColMaskArgs {
+  uint64_t seed;
+  int32_t tree;
+  int64_t F;
+  int32_t D;
+  const double* thr_tree;         // [1] or null
+  const double* thr_level;        // [D] or null
+  uint8_t* mask;                  // [D][F] out
 };
 
 FDX_HD int32_t rf_tree_of(const RfSampleArgs& a, int64_t i) { return a.node_trees ? a.node_trees[i] : a.tree; }
@@ -519,8 +553,15 @@ struct SplitArgs {
   const int32_t* sub_par;
   const int32_t* sub_sib;
   const int64_t* parent_hist;
+  // optional (GBDT column sampling): this level's row of ColMaskArgs mask -- feature f may split iff
+  // col_mask[fid_orig[f]] != 0 (it passes the tree stage and this level's stage) and it passes the
+  // node stage (feat_thr). Only the search is gated: the fused sibling subtraction still runs for
+  // every feature, so the next level's parents are complete.
+  const uint8_t* col_mask;
 };
 constexpr int32_t kSplitWide = 16;
+constexpr int32_t kColTreeKey = (int32_t)0xFFFFFFFFu;     // pseudo-node of the tree stage
+constexpr int32_t kColLevelKey = (int32_t)0xFFFFFFFEu;    // ... of level 0's stage (minus the depth)
 
 FDX_HD int64_t split_row(const SplitArgs& a, int n) { return a.row_of ? a.row_of[n] : n; }
 
@@ -646,6 +687,23 @@ FDX_HD double feature_priority(uint64_t seed, int32_t tree, int32_t node, int64_
   return hash_uniform(seed ^ 0x5bd1e995ull, ((uint64_t)(uint32_t)tree << 32) | (uint32_t)node, (uint64_t)fid);
 }
 
+// The outer stages of a filtered threshold search (RfSampleArgs n_outer) / of the split search.
+FDX_HD bool col_stage_pass(uint64_t seed, int32_t tree, int32_t key, int64_t fid, double thr) {
+  return feature_priority(seed, tree, key, fid) <= thr;
+}
+
+FDX_HD bool split_col_ok(const SplitArgs& a, int f) {
+  return !a.col_mask || a.col_mask[a.fid_orig[f]] != 0;
+}
+
+FDX_HD bool rf_outer_pass(const RfSampleArgs& a, int64_t f) { return !a.outer_mask || a.outer_mask[f] != 0; }
+
+FDX_HD uint8_t col_mask_at(const ColMaskArgs& a, int d, int64_t f) {
+  if (a.thr_tree && !col_stage_pass(a.seed, a.tree, kColTreeKey, f, *a.thr_tree)) return 0;
+  if (a.thr_level && !col_stage_pass(a.seed, a.tree, kColLevelKey - d, f, a.thr_level[d])) return 0;
+  return 1;
+}
+
 // The 53-bit integer behind feature_priority (priority == u * 2^-53 exactly).
 FDX_HD uint64_t feature_priority_u53(uint64_t seed, int32_t tree, int32_t node, int64_t fid) {
   const uint64_t x = mix64((seed ^ 0x5bd1e995ull) ^
@@ -693,12 +751,21 @@ FDX_HD int poisson1(double u) {
   return k;
 }
 
+// GBDT row subsampling: round a.tree keeps row r (every row without subsampling).
+FDX_HD bool row_kept(const QuantArgs& a, int64_t r) {
+  return !(a.subsample > 0.0 && a.subsample < 1.0) ||
+         hash_uniform(a.seed, (uint64_t)a.tree, (uint64_t)(a.row0 + r)) < a.subsample;
+}
+
 // The two statistics of one row before quantisation.
-FDX_HD void row_stats(const QuantArgs& a, int64_t r, double* v0, double* v1) {
+FDX_HD void row_stats(const QuantArgs& a, int64_t r, double* v0, double* v1, bool* kept = nullptr) {
   if (a.mode == 0) {
     const double w = a.weight ? (double)a.weight[r] : 1.0;
-    *v0 = (double)a.g[r] * w;
-    *v1 = (double)a.h[r] * w;
+    // (the loads are issued whether the row is kept or not: the hash is arithmetic only)
+    const bool keep = row_kept(a, r);
+    *v0 = keep ? (double)a.g[r] * w : 0.0;
+    *v1 = keep ? (double)a.h[r] * w : 0.0;
+    if (kept) *kept = keep;
   } else {
     double w = a.weight ? (double)a.weight[r] : 1.0;
     if (a.bootstrap) w *= (double)poisson1(hash_uniform(a.seed, (uint64_t)a.tree, (uint64_t)(a.row0 + r)));

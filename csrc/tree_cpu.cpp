@@ -57,6 +57,15 @@ void quant_cpu(const QuantArgs& a, const double* maxv) {
   });
   a.totals[0] = t0.load();
   a.totals[1] = t1.load();
+  if (a.keepbits)                            // a word per 64 rows, each written by one thread
+    parallel_for((a.N + 63) / 64, 0, 1 << 10, [&](int64_t lo, int64_t hi) {
+      for (int64_t w = lo; w < hi; ++w) {
+        uint64_t bits = 0;
+        for (int64_t r = 64 * w; r < 64 * (w + 1) && r < a.N; ++r)
+          if (row_kept(a, r)) bits |= 1ull << (r & 63);
+        a.keepbits[w] = bits;
+      }
+    });
 }
 
 void slot8_cpu(const SlotArgs& a) {
@@ -92,10 +101,15 @@ void rf_sample_cpu(const RfSampleArgs& a) {
   parallel_for(a.nnodes, 0, 1, [&](int64_t lo, int64_t hi) {
     std::vector<uint64_t> u((size_t)a.F);
     for (int64_t i = lo; i < hi; ++i) {
-      if (a.nodes[i] < 0) { a.thr[i] = -1.0; continue; }   // padding of a capacity-sized open list
-      for (int64_t f = 0; f < a.F; ++f) u[(size_t)f] = feature_priority_u53(a.seed, rf_tree_of(a, i), a.nodes[i], f);
-      std::nth_element(u.begin(), u.begin() + (a.k - 1), u.end());
-      a.thr[i] = (double)u[(size_t)(a.k - 1)] * (1.0 / 9007199254740992.0);
+      if (a.nodes[i] < 0 && !a.raw_keys) { a.thr[i] = -1.0; continue; }   // padding of a capacity-sized open list
+      size_t m = 0;                                   // (the features that pass the outer stages)
+      for (int64_t f = 0; f < a.F; ++f)
+        if (rf_outer_pass(a, f))
+          u[m++] = feature_priority_u53(a.seed, rf_tree_of(a, i), a.nodes[i], f);
+      const size_t kk = (size_t)a.k <= m ? (size_t)a.k : m;
+      if (kk == 0) { a.thr[i] = -1.0; continue; }
+      std::nth_element(u.begin(), u.begin() + (kk - 1), u.begin() + m);
+      a.thr[i] = (double)u[kk - 1] * (1.0 / 9007199254740992.0);
     }
   });
   parallel_for(a.Fa, 0, 4096, [&](int64_t lo, int64_t hi) {
@@ -107,6 +121,12 @@ void rf_sample_cpu(const RfSampleArgs& a) {
              a.thr[i]) ? 1 : 0;
       a.mask[f] = m;
     }
+  });
+}
+
+void col_mask_cpu(const ColMaskArgs& a) {
+  parallel_for((int64_t)a.D * a.F, 0, 1 << 14, [&](int64_t lo, int64_t hi) {
+    for (int64_t t = lo; t < hi; ++t) a.mask[t] = col_mask_at(a, (int)(t / a.F), t % a.F);
   });
 }
 
@@ -339,6 +359,7 @@ void split_cpu(const SplitArgs& a) {
       if (use && a.feat_thr)
         use = feature_priority(a.seed, a.node_tree ? a.node_tree[n] : a.tree, a.node_ids[n], a.fid_orig[f]) <=
               a.feat_thr[n];
+      if (use) use = split_col_ok(a, f);
       if (use) {
         const int64_t* hb = a.hist + (split_row(a, n) * (a.hist_stride ? a.hist_stride : a.boff[a.Fa]) + a.boff[f]) * 2;
         gain = best_split_scan(hb, a.nbins[f], a.zbin[f], a.totals[2 * n], a.totals[2 * n + 1], s0, s1, a.mode,

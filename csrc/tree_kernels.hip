@@ -222,14 +222,20 @@ __device__ __forceinline__ void quant_kernel_body(QuantArgs a, const double* max
   const int64_t step = (int64_t)gridDim.x * 256 * kPrologueU;
   for (int64_t r0 = (int64_t)blockIdx.x * 256 * kPrologueU + threadIdx.x; r0 < a.N; r0 += step) {
     double sv0[kPrologueU], sv1[kPrologueU];
+    bool kp[kPrologueU];
 #pragma unroll
     for (int u = 0; u < kPrologueU; ++u) {
       sv0[u] = sv1[u] = 0.0;
-      if (r0 + 256 * u < a.N) row_stats(a, r0 + 256 * u, &sv0[u], &sv1[u]);
+      kp[u] = false;
+      if (r0 + 256 * u < a.N) row_stats(a, r0 + 256 * u, &sv0[u], &sv1[u], &kp[u]);
     }
 #pragma unroll
     for (int u = 0; u < kPrologueU; ++u) {
       const int64_t r = r0 + 256 * u;
+      if (a.keepbits) {          // the wave's 64 consecutive rows: one ballot, one 64-bit store by lane 0
+        const unsigned long long bal = __ballot(kp[u]);
+        if ((threadIdx.x & 63) == 0 && r < a.N) a.keepbits[r >> 6] = bal;
+      }
       if (r >= a.N) break;
       const double v0 = sv0[u], v1 = sv1[u];
       const int64_t q0 = quantize_value(v0, k0), q1 = quantize_value(v1, k1);
@@ -953,10 +959,14 @@ __device__ __forceinline__ double split_narrow_at(const SplitArgs& a, int64_t t,
   double gain = -1.0 / 0.0;
   int bin = -1;
   int64_t l0 = 0, l1 = 0;
-  bool use = a.node_ids[n] >= 0;              // -1: padded row of a device level loop
+  const bool live = a.node_ids[n] >= 0;       // -1: padded row of a device level loop
+  bool use = live;
   if (use && a.feat_thr)
     use = split_priority(a, n, f) <= a.feat_thr[n];
-  if (use) {
+  if (use) use = split_col_ok(a, f);
+  // (feature sampling gates the search alone: the fused sibling subtraction runs for every feature
+  // of a live node, so the next level's parent rows are complete)
+  if (use || (live && a.sub_of != nullptr)) {
     const int64_t stride = a.hist_stride ? a.hist_stride : a.boff[a.Fa];
     const int64_t* hb = a.hist + (split_row(a, n) * stride + a.boff[f]) * 2;
     const int32_t k = a.sub_of ? a.sub_of[n] : -1;
@@ -966,10 +976,12 @@ __device__ __forceinline__ double split_narrow_at(const SplitArgs& a, int64_t t,
       int64_t* ob = const_cast<int64_t*>(hb);
       for (int b = 0; b < 2 * a.nbins[f]; ++b) ob[b] = pb[b] - sb[b];
     }
-    int64_t T0, T1;
-    split_totals(a, n, &T0, &T1);
-    gain = best_split_scan(hb, a.nbins[f], a.zbin[f], T0, T1, ldexp(1.0, -a.kexp[0]),
-                           ldexp(1.0, -a.kexp[1]), a.mode, a.lambda_, a.min_child_weight, &bin, &l0, &l1);
+    if (use) {
+      int64_t T0, T1;
+      split_totals(a, n, &T0, &T1);
+      gain = best_split_scan(hb, a.nbins[f], a.zbin[f], T0, T1, ldexp(1.0, -a.kexp[0]),
+                             ldexp(1.0, -a.kexp[1]), a.mode, a.lambda_, a.min_child_weight, &bin, &l0, &l1);
+    }
   }
   a.out_gain[t] = gain;
   a.out_bin[t] = bin;
@@ -1041,13 +1053,15 @@ __device__ __forceinline__ void split_wide_at(const SplitArgs& a, int64_t w, int
   if (w >= (int64_t)a.num_nodes * a.n_wide) return;                 // (wave-uniform)
   const int n = (int)(w / a.n_wide), f = a.wide[w % a.n_wide];
   const int64_t t = (int64_t)n * a.Fa + f;
-  bool use = a.node_ids[n] >= 0;
+  const bool live = a.node_ids[n] >= 0;
+  bool use = live;
   if (use && a.feat_thr)
     use = split_priority(a, n, f) <= a.feat_thr[n];
+  if (use) use = split_col_ok(a, f);
   double best = -1.0 / 0.0;
   int best_b = -1;
   int64_t bl0 = 0, bl1 = 0;
-  if (use) {
+  if (use || (live && a.sub_of != nullptr)) {   // (split_narrow_at: the subtraction is never gated)
     const int64_t stride = a.hist_stride ? a.hist_stride : a.boff[a.Fa];
     const int64_t* hb = a.hist + (split_row(a, n) * stride + a.boff[f]) * 2;
     const int nb = a.nbins[f], zb = a.zbin[f];
@@ -1063,6 +1077,7 @@ __device__ __forceinline__ void split_wide_at(const SplitArgs& a, int64_t w, int
       __threadfence_block();
       __builtin_amdgcn_wave_barrier();
     }
+    if (use) {                     // (wave-uniform)
     int64_t T0, T1;
     split_totals(a, n, &T0, &T1);
     const double s0 = ldexp(1.0, -a.kexp[0]), s1 = ldexp(1.0, -a.kexp[1]);
@@ -1101,6 +1116,7 @@ __device__ __forceinline__ void split_wide_at(const SplitArgs& a, int64_t w, int
       if (ob >= 0 && (best_b < 0 || og > best || (og == best && ob < best_b))) {
         best = og; best_b = ob; bl0 = o0; bl1 = o1;
       }
+    }
     }
   }
   if (lane == 0) {

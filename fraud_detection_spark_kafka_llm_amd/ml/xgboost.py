@@ -55,8 +55,18 @@ class _XGBParams:
                Param("objective", "objective", "binary:logistic", str),
                Param("tree_method", "tree method", "hist", str),
                Param("seed", "random seed", 0, int),
+               Param("subsample", "fraction of the rows each boosting round keeps, in (0, 1]", 1.0, float),
+               Param("colsample_bytree", "fraction of the features each tree may split on, in (0, 1]", 1.0, float),
+               Param("colsample_bylevel", "fraction of the tree's features each level may split on", 1.0, float),
+               Param("colsample_bynode", "fraction of the level's features each node may split on", 1.0, float),
+               Param("sampling_method", "row sampling method (only 'uniform')", "uniform", str),
                Param("deterministic", "accepted for compatibility: training is always bitwise reproducible", True,
                      bool)]
+
+    # defaults that are not written to ``defaultParamMap``: the metadata of a model that never set
+    # them keeps the bytes it had before these parameters existed (a set value goes to ``paramMap``)
+    _persist_defaults_only = ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode",
+                              "sampling_method")
 
     # ClassificationModelBase reads Spark-style column getters
     def getFeaturesCol(self):  # noqa: N802
@@ -104,16 +114,23 @@ class SparkXGBClassifier(_XGBParams, Estimator):
         super().__init__(**kw)
 
     def _fit(self, frame: Frame) -> "SparkXGBClassifierModel":
-        from ..models.gbdt import GBDTParams, fit_gbdt
+        from ..models.gbdt import GBDTParams, check_sampling, fit_gbdt
 
         if self.getOrDefault("objective") != "binary:logistic":
             raise NotImplementedError("only objective='binary:logistic' is supported")
+        if self.getOrDefault("sampling_method") != "uniform":
+            raise NotImplementedError("only sampling_method='uniform' is supported")
         p = GBDTParams(n_estimators=self.getOrDefault("n_estimators"), max_depth=self.getOrDefault("max_depth"),
                        learning_rate=self.getOrDefault("learning_rate"), reg_lambda=self.getOrDefault("reg_lambda"),
                        gamma=self.getOrDefault("gamma"), min_child_weight=self.getOrDefault("min_child_weight"),
                        max_bin=self.getOrDefault("max_bin"), max_delta_step=self.getOrDefault("max_delta_step"),
                        base_score=self._paramMap.get("base_score"), seed=self.getOrDefault("seed"),
-                       deterministic=bool(self.getOrDefault("deterministic")))
+                       deterministic=bool(self.getOrDefault("deterministic")),
+                       subsample=self.getOrDefault("subsample"),
+                       colsample_bytree=self.getOrDefault("colsample_bytree"),
+                       colsample_bylevel=self.getOrDefault("colsample_bylevel"),
+                       colsample_bynode=self.getOrDefault("colsample_bynode"))
+        check_sampling(p)
         w = frame.column(self.getOrDefault("weight_col")) if self.isSet("weight_col") else None
         X, y = frame.column(self.getFeaturesCol()), frame.column(self.getLabelCol())
         # validation rows (xgboost.spark's validation_indicator_col): split off before training, so

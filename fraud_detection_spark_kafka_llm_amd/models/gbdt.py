@@ -50,6 +50,25 @@ class GBDTParams:
     # Accepted for API compatibility: training is always bitwise reproducible for any world size
     # and work split (exact int64 histograms of quantised g, h; see models/grower.py).
     deterministic: bool = True
+    # stochastic boosting: round t keeps the row with global index i iff
+    # hash_uniform(seed, t, i) < subsample (models/rf_sampling.row_keep_mask)
+    subsample: float = 1.0
+    # nested column sampling as xgboost's: exactly max(1, int(fraction * n)) of the n features the
+    # stage before keeps, per tree, per level and per node (models/rf_sampling.column_thresholds)
+    colsample_bytree: float = 1.0
+    colsample_bylevel: float = 1.0
+    colsample_bynode: float = 1.0
+
+
+SAMPLING_PARAMS = ("subsample", "colsample_bytree", "colsample_bylevel", "colsample_bynode")
+
+
+def check_sampling(params: "GBDTParams") -> None:
+    """The four sampling fractions must lie in (0, 1]; checked before any work starts."""
+    for name in SAMPLING_PARAMS:
+        v = getattr(params, name)
+        if v is None or isinstance(v, (bool, str)) or not (0.0 < float(v) <= 1.0):
+            raise ValueError(f"{name} must be in (0, 1], got {v!r}")
 
 
 @dataclass
@@ -91,6 +110,7 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
     from ..parallel.checkpoint import EnsembleCheckpointer, data_fingerprint, maybe_fail
     from .monitor import ValidationMonitor, check_eval_args
 
+    check_sampling(params)
     if eval_set is not None:
         check_eval_args(eval_set, eval_metric, early_stopping_rounds)
     C = native.lib()
@@ -123,7 +143,9 @@ def fit_gbdt(features, labels, params: GBDTParams = GBDTParams(), device=None, w
     margin = torch.full((N,), base, dtype=torch.float64, device=dev)
     gp = GrowParams(max_depth=params.max_depth, mode=0, lambda_=params.reg_lambda, min_child=params.min_child_weight,
                     min_gain=params.gamma, seed=params.seed, eta=params.learning_rate,
-                    max_delta_step=params.max_delta_step)
+                    max_delta_step=params.max_delta_step, subsample=float(params.subsample),
+                    colsample_bytree=float(params.colsample_bytree), colsample_bylevel=float(params.colsample_bylevel),
+                    colsample_bynode=float(params.colsample_bynode))
     with tracing.span("gbdt.workspace"):
         ws = Workspace(Q)
     trees = list(start_trees or [])

@@ -156,6 +156,15 @@ class Workspace:
             self.rg_listdig = torch.empty((self.Q.n_rows, 2), dtype=torch.int32, device=self.dev)
         return rg
 
+    def keepbits(self, params) -> Optional[torch.Tensor]:
+        """[ceil(N / 64)] int64: one keep bit per row of a subsampled GBDT round, written by the
+        quantisation (a ballot per 64 rows) and read by the row lists (None without subsampling)."""
+        if params.mode != 0 or params.subsample >= 1.0:
+            return None
+        if getattr(self, "_keepbits", None) is None:
+            self._keepbits = torch.zeros((self.Q.n_rows + 63) // 64, dtype=torch.int64, device=self.dev)
+        return self._keepbits
+
     def rg_emdig(self) -> torch.Tensor:
         """[N, 2] digit words zeroed outside the one built node (entry-major listed pass)."""
         if getattr(self, "_rg_emdig", None) is None:
@@ -349,9 +358,76 @@ def pass_ct(np_: int, cnt: int) -> int:
     return ct
 
 
+class ColumnSampler:
+    """GBDT column sampling of one workspace (models/rf_sampling.column_thresholds is its oracle):
+    the stage counts, the device thresholds of the tree stage [1], of every level's stage [D] and of
+    a level's open nodes [2^D], the pseudo-node keys, and the [D, F] byte mask of the tree and level
+    stages that the node-stage searches and the split search read (one byte per feature index,
+    written once per tree). The native runner fills and reads the tensors itself
+    (RfLevels.col_begin / col_level); ``begin`` / ``level_args`` are the same launches for the
+    Python loops (device or host twins). Nothing is allocated unless a fraction is < 1."""
+
+    @classmethod
+    def of(cls, Q: Quantized, ws: "Workspace", params: GrowParams) -> Optional["ColumnSampler"]:
+        fr = (params.colsample_bytree, params.colsample_bylevel, params.colsample_bynode)
+        if params.mode != 0 or all(f >= 1.0 for f in fr):
+            return None
+        key = (fr, params.max_depth)
+        cur = getattr(ws, "_col", None)
+        if cur is None or cur.key != key:
+            cur = ws._col = cls(Q, params, key)
+        return cur if cur.on else None
+
+    def __init__(self, Q: Quantized, params: GrowParams, key):
+        from . import rf_sampling
+
+        dev, D = Q.device, max(int(params.max_depth), 1)
+        self.key, self.F, self.D = key, int(Q.num_features), D
+        self.ks = rf_sampling.column_counts(self.F, *key[0])
+        self.on = any(self.ks)
+        f64 = lambda n: torch.ones(n, dtype=torch.float64, device=dev)   # noqa: E731
+        self.tree, self.level, self.node = f64(1), f64(D), f64(2 ** D)
+        self.tkey = torch.tensor([-1], dtype=torch.int32, device=dev)          # 0xFFFFFFFF
+        self.lkeys = torch.tensor([-2 - d for d in range(D)], dtype=torch.int32, device=dev)   # 0xFFFFFFFE - d
+        outer = bool(self.ks[0] or self.ks[1])
+        self.mask = torch.empty((D, self.F), dtype=torch.uint8, device=dev) if outer else None
+        # features that pass the tree stage / the tree and level stages (the searches' populations)
+        self.pop1 = self.ks[0] or self.F
+        self.pop2 = self.ks[1] or self.pop1
+
+    def nbytes(self) -> int:
+        return int(self.mask.numel()) if self.mask is not None else 0
+
+    def runner_cfg(self) -> dict:
+        return dict(col_k=list(self.ks), col_tree=self.tree, col_level=self.level, col_node=self.node,
+                    col_tkey=self.tkey, col_lkeys=self.lkeys, col_mask=self.mask)
+
+    def begin(self, C, seed: int, tree: int) -> None:
+        if self.mask is None:
+            return
+        t = self.tree if self.ks[0] else None
+        if self.ks[0]:
+            C.tree_col_thresholds(seed, tree, self.tkey, True, self.F, self.ks[0], self.tree, pop=self.F)
+        if self.ks[0] and self.ks[1]:      # row 0 = the tree stage alone, for the level searches
+            C.tree_col_mask(seed, tree, t, None, self.mask[:1])
+        if self.ks[1]:
+            C.tree_col_thresholds(seed, tree, self.lkeys, True, self.F, self.ks[1], self.level,
+                                  outer_mask=self.mask[0] if self.ks[0] else None, pop=self.pop1)
+        C.tree_col_mask(seed, tree, t, self.level if self.ks[1] else None, self.mask)
+
+    def level_args(self, C, seed: int, tree: int, d: int, open_ids: torch.Tensor) -> tuple:
+        """(node-stage thresholds of the open nodes or None, tree_split_find's column arguments)."""
+        thr = None
+        if self.ks[2]:
+            thr = self.node[:open_ids.numel()]
+            C.tree_col_thresholds(seed, tree, open_ids, False, self.F, self.ks[2], thr,
+                                  outer_mask=self.mask[d] if self.mask is not None else None, pop=self.pop2)
+        return thr, (dict(col_mask=self.mask[d]) if self.mask is not None else {})
+
+
 def _best_splits(C, hist, totals, boff, nbins, zbin, fid_orig, node_ids, kexp, params, feat_thr, tree_index, Fa,
                  f0, node_tree=None, cache: Optional[dict] = None, out: Optional[torch.Tensor] = None,
-                 row_of: Optional[torch.Tensor] = None):
+                 row_of: Optional[torch.Tensor] = None, **col_kw):
     """Per node: (gain float64, feature (+f0) int64, bin int64, left sums int64 [2]) of the best
     split over Fa features of ``hist`` [nodes, boff[Fa], 2]; gain -inf without a valid candidate.
     Returned as one int64 tensor [nodes, 5] (gain bit-cast) for a single device->host copy.
@@ -382,7 +458,7 @@ def _best_splits(C, hist, totals, boff, nbins, zbin, fid_orig, node_ids, kexp, p
     wide = _wide_features(nbins, Fa) if dev.type == "cuda" else None
     C.tree_split_find(hist, totals, boff, nbins, zbin, fid_orig, node_ids, kexp, int(params.mode),
                       float(params.lambda_), float(params.min_child), feat_thr, int(params.seed), int(tree_index),
-                      out_gain, out_bin, out_left, node_tree, wide, row_of)
+                      out_gain, out_bin, out_left, node_tree, wide, row_of, **col_kw)
     # best gain per node, ties to the lowest feature index (deterministic whatever the batch shape):
     # one native reduction instead of ~9 small torch launches per level
     if out is None:
@@ -435,7 +511,7 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
                              ws.maxabs, Q.row0)
             mx = coll.max(ws.maxabs) if use_coll else ws.maxabs
             C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 4, mx, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0)
+                         ws.kexp, ws.totals, ws.digp, Q.row0, float(params.subsample), ws.keepbits(params))
         else:
             C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 1, None, ws.rowdig,
                          ws.kexp, ws.totals, ws.digp, Q.row0)
@@ -450,6 +526,9 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
     prev_index: dict = {}
     TB = Q.TB
     feat_thr_all = None
+    col = ColumnSampler.of(Q, ws, params)
+    if col is not None:
+        col.begin(C, int(params.seed), int(tree_index))
 
     for d in range(params.max_depth + 1):
         open_nodes = [n for n in level if not is_leaf[n]]
@@ -557,13 +636,16 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
                                 gfid, gden, h_boff, Q.nbins, s2n, hist_target, h_stride, Q.n_rows, rr, bt, ct, np_))
                 ws.run_concurrent(launches)
         totals, node_ids = up[h_tot], up[h_ids]
+        col_kw = {}
+        if col is not None:         # (the node stage rides in feat_thr, as RF's per-node sample does)
+            feat_thr, col_kw = col.level_args(C, int(params.seed), int(tree_index), d, node_ids)
         sub_t = tuple(up[h] for h in h_sub) if h_sub is not None else None
         if shards is None:
             if sub_t is not None:
                 C.tree_hist_subtract(prev_hist, cur_hist, *sub_t, TB)
             with tracing.span("tree.split"):
                 packed = _best_splits(C, cur_hist, totals, Q.boff, Q.nbins, Q.zbin, Q.fid_orig, node_ids, ws.kexp,
-                                      params, feat_thr, tree_index, Q.Fa, 0)
+                                      params, feat_thr, tree_index, Q.Fa, 0, **col_kw)
                 packed = packed.cpu().numpy()
         else:
             with tracing.span("tree.reduce_scatter"), _CollTimer(dev):
@@ -582,7 +664,7 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
                 C.tree_hist_subtract(prev_hist, cur_hist, *sub_t, shards.Bs)
             with tracing.span("tree.split"):
                 mine = _best_splits(C, cur_hist, totals, shards.boff, shards.nbins, shards.zbin, shards.fid_orig,
-                                    node_ids, ws.kexp, params, feat_thr, tree_index, shards.Fa, shards.f0)
+                                    node_ids, ws.kexp, params, feat_thr, tree_index, shards.Fa, shards.f0, **col_kw)
                 with _CollTimer(dev):
                     allt = coll.all_gather(mine)                              # [S, nl, 5]
                 gains = allt[:, :, 0].contiguous().view(torch.float64)
@@ -729,7 +811,8 @@ def _level_runner(Q: Quantized, ws: Workspace, st: "LevelState", params: GrowPar
     level state and tree parameters. RF (``sampled``): every kernel of a level; GBDT: the tree
     prologue, the fused split + plan and the partition (the row-group passes stay in Python)."""
     key = (params.mode, params.max_depth, params.min_gain, params.min_child, params.seed, params.feat_k,
-           params.lambda_, sampled)
+           params.lambda_, sampled, params.subsample, params.colsample_bytree, params.colsample_bylevel,
+           params.colsample_bynode)
     cached = getattr(ws, "_rf_runner", None)
     if cached is not None and cached[0] is st and cached[1] == key:
         return cached[2]
@@ -747,9 +830,14 @@ def _level_runner(Q: Quantized, ws: Workspace, st: "LevelState", params: GrowPar
                cs_bin=st.cs[3], cs_left_default=st.cs[4], node_slot=st.node_slot, s2n=st.s2n, sub_dst=st.sub_dst,
                sub_par=st.sub_par, sub_sib=st.sub_sib, sub_of=st.sub_of, node_dense=st.node_dense, mode=int(params.mode),
                max_depth=int(params.max_depth), min_gain=float(params.min_gain), lambda_=float(params.lambda_),
-               mcw=float(params.min_child), seed=int(params.seed), F=int(Q.num_features), k=int(params.feat_k),
+               mcw=float(params.min_child), seed=int(params.seed), subsample=float(params.subsample),
+               keepbits=ws.keepbits(params),
+               F=int(Q.num_features), k=int(params.feat_k),
                lds=bool(RF_LDS), wps=int(PARTITION_WPS), arena=st.arena, dig16=ws.dig16() if sampled else None,
                fmix=_feature_mix(Q) if (params.feat_k and FEATURE_MIX) else None)
+    col = ColumnSampler.of(Q, ws, params)
+    if col is not None:
+        cfg.update(col.runner_cfg())
     runner = native.lib().RfLevels(cfg)
     ws._rf_runner = (st, key, runner)
     return runner
@@ -930,7 +1018,7 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                              ws.maxabs, Q.row0)
             mx = coll.max(ws.maxabs) if coll is not None else ws.maxabs
             C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 4, mx, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0)
+                         ws.kexp, ws.totals, ws.digp, Q.row0, float(params.subsample), ws.keepbits(params))
         else:
             C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 1, None, ws.rowdig,
                          ws.kexp, ws.totals, ws.digp, Q.row0)
@@ -943,6 +1031,13 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
         tot = coll.sum(ws.totals) if coll is not None else ws.totals
         st.stats[0].copy_(tot)
         st.totals[0][:1].copy_(tot[None])
+    # GBDT column sampling: the tree's and every level's stage thresholds, queued behind the prologue
+    col = ColumnSampler.of(Q, ws, params)
+    if col is not None:
+        if runner is not None:
+            runner.col_begin(int(tree_index))
+        else:
+            col.begin(C, seed, int(tree_index))
     n_open, n_build = 1, 1
     prev_hist = prev_row_of = None
     ev = None
@@ -1007,6 +1102,11 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
             feat_mask = torch.empty(Q.Fa, dtype=torch.uint8, device=dev)
             C.tree_rf_sample(seed, int(tree_index), open_d, int(Q.num_features), int(params.feat_k), Q.fid_orig,
                              feat_thr, feat_mask, None)
+        col_kw = {}
+        if col is not None and runner is not None:
+            runner.col_level(d, open_d, int(tree_index))       # (node stage queued; find() reads the tables)
+        elif col is not None:
+            feat_thr, col_kw = col.level_args(C, seed, int(tree_index), d, open_d)
         split_boff = shards.boff if shards is not None else None
         bufs = None
         if shards is None:
@@ -1079,7 +1179,8 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
                     emdig = ws.rg_emdig() if (n_build == 1 and rg.erow is not None and qmod.RG_EM_MIN_FRAC <= 1.0) \
                         else None
                     C.tree_rg_list(ws.row_node, st.node_slot, None, Q.n_rows, n_build, ws.rg_work, ws.rg_start,
-                                   ws.rg_list, ws.rowdig, ws.rg_listdig, emdig, counted=rg_counted)
+                                   ws.rg_list, ws.rowdig, ws.rg_listdig, emdig, counted=rg_counted,
+                                   keepbits=ws.keepbits(params))
                     C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, np_, ws.rg_list, ws.rg_start,
                                    ws.rg_listdig, n_build, rg.gmode, wtab, s2n, hist_target, h_stride,
                                    *shard_args, RG_DBG, **(rg.em_args(emdig) if emdig is not None else {}), **part)
@@ -1182,15 +1283,15 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
             elif runner is not None:
                 runner.split(cur_hist, totals_d, split_boff, shards.nbins, shards.zbin, shards.fid_orig, open_d,
                              feat_thr, int(tree_index), shards.f0, bufs.ag_in, row_of,
-                             _wide_features(shards.nbins, shards.Fa))
+                             _wide_features(shards.nbins, shards.Fa), d if col is not None else -1)
                 packed = yield CollStep("ag")
             elif shards is None:
                 packed = _best_splits(C, cur_hist, totals_d, Q.boff, Q.nbins, Q.zbin, Q.fid_orig, open_d, ws.kexp,
-                                      params, feat_thr, tree_index, Q.Fa, 0, cache=ws.split_cache)
+                                      params, feat_thr, tree_index, Q.Fa, 0, cache=ws.split_cache, **col_kw)
             else:
                 _best_splits(C, cur_hist, totals_d, split_boff, shards.nbins, shards.zbin, shards.fid_orig,
                              open_d, ws.kexp, params, feat_thr, tree_index, shards.Fa, shards.f0,
-                             cache=ws.split_cache, out=bufs.ag_in, row_of=row_of)
+                             cache=ws.split_cache, out=bufs.ag_in, row_of=row_of, **col_kw)
                 # [S, n_open, 5] (the batch's all-gather): tree_level_plan takes the best over
                 # shards per node (ties to the lowest shard = the lowest feature)
                 packed = yield CollStep("ag")

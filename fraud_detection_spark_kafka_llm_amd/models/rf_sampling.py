@@ -86,3 +86,70 @@ def level_feature_mask(Q, seed: int, tree_index: int, nodes: list, thr: torch.Te
     for i, n in enumerate(nodes):
         mask |= _priorities(seed, tree_index, n, fid) <= thr[i]
     return mask
+
+
+def row_keep_mask(seed: int, round_index: int, row0: int, n: int, subsample: float, dev="cpu") -> torch.Tensor:
+    """[n] bool: the rows a GBDT round keeps under row subsampling -- global row ``row0 + r`` is kept
+    iff ``hash_uniform(seed, round, row0 + r) < subsample`` (``row_stats`` in csrc/tree.h; every row
+    when ``subsample`` is 1). Stateless: the same on host and device, on every rank and at every
+    world size."""
+    if subsample >= 1.0:
+        return torch.ones(n, dtype=torch.bool, device=dev)
+    rows = torch.arange(int(row0), int(row0) + n, dtype=torch.int64, device=dev)
+    return hash_uniform(_u64(int(seed)), _u64(int(round_index) & 0xFFFFFFFFFFFFFFFF), rows) < float(subsample)
+
+
+# ---------------------------------------------------------------------------- GBDT column sampling
+COL_TREE_KEY = 0xFFFFFFFF          # pseudo-node of the tree stage
+COL_LEVEL_KEY = 0xFFFFFFFE         # ... of level 0's stage; level d uses COL_LEVEL_KEY - d
+
+
+def column_counts(num_features: int, colsample_bytree: float, colsample_bylevel: float,
+                  colsample_bynode: float) -> tuple:
+    """(k_tree, k_level, k_node): features each nested stage keeps, ``max(1, int(fraction * n))`` of
+    the n features the stage before it keeps (xgboost's column sampler); 0 for a stage that is
+    skipped -- its fraction is 1.0 (or it keeps every one of the F features): threshold 1.0."""
+    n, out = int(num_features), []
+    for frac in (colsample_bytree, colsample_bylevel, colsample_bynode):
+        if float(frac) >= 1.0:
+            out.append(0)
+            continue
+        n = max(1, int(float(frac) * n))
+        out.append(n if n < int(num_features) else 0)
+    return tuple(out)
+
+
+def _signed32(key: int) -> int:
+    key &= 0xFFFFFFFF
+    return key - (1 << 32) if key >= (1 << 31) else key
+
+
+def column_thresholds(num_features: int, seed: int, tree_index: int, depth: int, nodes: list,
+                      colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0, colsample_bynode: float = 1.0,
+                      dev="cpu") -> tuple:
+    """(thr_tree, thr_level, thr_node [len(nodes)], eligible [len(nodes), F] bool) of the level at
+    ``depth`` whose open nodes have the node-table ids ``nodes``: each stage's threshold is the
+    k-th smallest priority (``feature_priority``: key = the stage's pseudo-node, or the node id)
+    over the features that pass the stages before it; a feature may split node n iff its three
+    priorities are <= the three thresholds. A skipped stage has threshold 1.0."""
+    F = int(num_features)
+    k_tree, k_level, k_node = column_counts(F, colsample_bytree, colsample_bylevel, colsample_bynode)
+    fid = torch.arange(F, dtype=torch.int64, device=dev)
+    ok = torch.ones(F, dtype=torch.bool, device=dev)
+    thr_tree = thr_level = 1.0
+    if k_tree:
+        pr = _priorities(seed, tree_index, COL_TREE_KEY, fid)
+        thr_tree = float(torch.kthvalue(pr, k_tree).values)
+        ok &= pr <= thr_tree
+    if k_level:
+        pr = _priorities(seed, tree_index, COL_LEVEL_KEY - int(depth), fid)
+        thr_level = float(torch.kthvalue(pr[ok], k_level).values)
+        ok &= pr <= thr_level
+    thr_node = torch.ones(len(nodes), dtype=torch.float64, device=dev)
+    eligible = ok[None, :].repeat(len(nodes), 1)
+    if k_node:
+        for i, n in enumerate(nodes):
+            pr = _priorities(seed, tree_index, int(n), fid)
+            thr_node[i] = torch.kthvalue(pr[ok], k_node).values
+            eligible[i] &= pr <= thr_node[i]
+    return thr_tree, thr_level, thr_node, eligible

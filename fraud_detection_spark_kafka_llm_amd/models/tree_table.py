@@ -26,6 +26,13 @@ class GrowParams:
     seed: int = 0
     eta: float = 0.3              # gbdt learning rate (applied to leaf values)
     max_delta_step: float = 0.0
+    # gbdt: fraction of the rows each round keeps (models/rf_sampling.row_keep_mask); a row that is
+    # not kept has g = h = 0 for that tree and is still partitioned and scored
+    subsample: float = 1.0
+    # gbdt: nested column sampling, exactly k features a stage (models/rf_sampling.column_thresholds)
+    colsample_bytree: float = 1.0
+    colsample_bylevel: float = 1.0
+    colsample_bynode: float = 1.0
 
 
 class TreeTable:

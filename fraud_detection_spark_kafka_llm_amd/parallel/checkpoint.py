@@ -108,6 +108,9 @@ class EnsembleCheckpointer:
     is refused."""
 
     IGNORED = ("n_estimators", "num_trees", "base_score", "deterministic")
+    # parameters newer than some checkpoints: a key that is missing on either side compares as
+    # this default (a run that never sampled rows resumes a checkpoint written before the key existed)
+    DEFAULTS = {"subsample": 1.0, "colsample_bytree": 1.0, "colsample_bylevel": 1.0, "colsample_bynode": 1.0}
 
     def __init__(self, directory: str, every: int = 10, kind: str = "gbdt", data_id: str = "",
                  params: Optional[dict] = None):
@@ -153,7 +156,8 @@ class EnsembleCheckpointer:
             raise RuntimeError(f"checkpoint {cur} was written for different data ({st['data_id']} != {self.data_id})")
         if self.params is not None and isinstance(st.get("params"), dict):
             diff = sorted(k for k in set(self.params) | set(st["params"])
-                          if k not in self.IGNORED and self.params.get(k) != st["params"].get(k))
+                          if k not in self.IGNORED and
+                          self.params.get(k, self.DEFAULTS.get(k)) != st["params"].get(k, self.DEFAULTS.get(k)))
             if diff:
                 raise RuntimeError(f"checkpoint {cur} was written with different parameters: {diff}")
         return st

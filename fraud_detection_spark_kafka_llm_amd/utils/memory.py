@@ -53,6 +53,8 @@ CHUNK_SCRATCH_BYTES = 4.0   # fused featurizer CSR scratch per text byte (scorin
 CHUNK_ENTRY_TEMP = 48.0     # per chunk entry: compaction int64 step + position + gathered entries,
                             # and the chunk's radix-sort temporaries
 LEVEL_HIST_BYTES = 16.0     # (g, h) int64 sums per bin per node built in one level
+KEEP_BIT_BYTES = 1.0 / 8.0  # row subsampling: one keep bit per row (grower.Workspace.keepbits)
+COL_MASK_BYTES = 1.0        # column sampling: one byte per feature index and tree level (grower.ColumnSampler)
 RF_LANE_ROW_BYTES = 27.0    # RF: per tree in flight (models/forest_batch.py lanes), its workspace:
                             # digit words, masked digits, row -> node, packed row state, slots
                             # (~0.27 GB per lane at 10M rows, profiles/r4/rf500_sweep_*.json)
@@ -95,8 +97,10 @@ def featurize_bytes(rows: int, nnz: int, text_bytes_per_row: float = DEFAULT_BYT
 def training_bytes(rows: int, nnz: int, hot_features: int = DEFAULT_HOT_FEATURES, total_bins: int = 0,
                    built_nodes: int = DEFAULT_BUILT_NODES, groups: int = DEFAULT_GROUPS,
                    sparse_frac: float = DEFAULT_SPARSE_FRAC, rf_lanes: int = 0, n_val: int = 0,
-                   val_nnz: int = 0) -> float:
+                   val_nnz: int = 0, subsample: bool = False, col_features: int = 0, col_depth: int = 6) -> float:
     """Peak bytes of training (GBDT, row-group engine) on ``rows`` rows with ``nnz`` entries.
+    ``subsample``: a fit with row subsampling (its keep bits); ``col_features`` > 0: one with column
+    sampling over that many feature indices (its per-level byte mask).
     ``rf_lanes`` > 0: a RandomForest with that many trees in flight instead (its CSC work items
     and a workspace per lane on top of the shared state). ``n_val`` > 0: plus the validation set
     of a monitored GBDT fit (``validation_bytes``)."""
@@ -105,8 +109,10 @@ def training_bytes(rows: int, nnz: int, hot_features: int = DEFAULT_HOT_FEATURES
     if rf_lanes > 0:
         per_entry += ORDER_BYTES
         per_row += RF_LANE_ROW_BYTES * rf_lanes
+    if subsample:
+        per_row += KEEP_BIT_BYTES
     return per_entry * nnz + per_row * rows + LEVEL_HIST_BYTES * total_bins * built_nodes * 2 \
-        + validation_bytes(n_val, val_nnz)
+        + validation_bytes(n_val, val_nnz) + COL_MASK_BYTES * col_features * col_depth
 
 
 def validation_bytes(n_val: int, val_nnz: int = 0) -> float:
