@@ -24,11 +24,12 @@ def main():
     ap.add_argument("--docs", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--scorer", default="lr", choices=["none", "lr", "trees"])
+    ap.add_argument("--ngram", type=int, default=1, help="NGram width between the remover and HashingTF")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     pt, y = synth.generate(synth.SynthConfig(n=args.docs, seed=5), device=dev)
     F = 1 << 18
-    spec = T.FeatureSpec(clean=True, stopwords=list(ENGLISH), num_features=F)
+    spec = T.FeatureSpec(clean=True, stopwords=list(ENGLISH), num_features=F, ngram=args.ngram)
     rng = np.random.default_rng(0)
     idf = torch.from_numpy(rng.random(F)).to(dev)
     lr = T.LinearScorer(rng.normal(size=F), -1.0) if args.scorer == "lr" else None
@@ -46,7 +47,7 @@ def main():
         r = T.featurize_score(pt, spec, idf=idf, lr=lr, trees=trees, device=dev, fix_fallbacks=False)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
-    out = {"docs": args.docs, "bytes_per_doc": pt.nbytes / args.docs, "scorer": args.scorer,
+    out = {"docs": args.docs, "bytes_per_doc": pt.nbytes / args.docs, "scorer": args.scorer, "ngram": args.ngram,
            "device_ms": dt * 1e3, "device_docs_per_s": args.docs / dt, "device_text_GBps": pt.nbytes / dt / 1e9}
     # streaming path: pinned host -> device -> score -> host
     host = pt.to("cpu")

@@ -24,11 +24,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--ngram", type=int, default=1, help="NGram width between the remover and HashingTF")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B = args.batch
     F = 1 << 18
-    spec = T.FeatureSpec(clean=True, stopwords=list(ENGLISH), num_features=F)
+    spec = T.FeatureSpec(clean=True, stopwords=list(ENGLISH), num_features=F, ngram=args.ngram)
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
     from test_text_featurizer import random_forest_arrays
 

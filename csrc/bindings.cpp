@@ -91,7 +91,8 @@ fdx::TreeEnsemble make_trees(const optional<std::vector<Tensor>>& tr, int64_t K,
 }
 
 // CountVectorizer fit (K-05): per kept token a 64-bit key (murmur3 seed 42 << 32 | murmur3 seed 2)
-// after clean / tokenize / stop-word removal. Without key_off/out_keys only the per-document token
+// after clean / tokenize / stop-word removal (per n-gram of the kept tokens when the flags carry an
+// NGram width). Without key_off/out_keys only the per-document token
 // counts are written (pass 1); with them the keys land at key_off[d] + i (pass 2).
 void token_keys(const Tensor& text, const Tensor& doc_off, int64_t flags, const optional<std::vector<Tensor>>& stop,
                 const Tensor& out_ntok, const Tensor& out_status, const optional<Tensor>& key_off,
@@ -116,7 +117,8 @@ void token_keys(const Tensor& text, const Tensor& doc_off, int64_t flags, const 
   a.text = text.data_ptr<uint8_t>();
   a.doc_off = doc_off.data_ptr<int64_t>();
   a.num_docs = (int32_t)D;
-  a.flags = (int32_t)((flags & (fdx::kFlagClean | fdx::kFlagPreLowered | fdx::kFlagStopwords)) | fdx::kFlagKeys);
+  a.flags = (int32_t)((flags & (fdx::kFlagClean | fdx::kFlagPreLowered | fdx::kFlagStopwords | fdx::kNgramMask)) |
+                        fdx::kFlagKeys);
   a.num_features = 1;
   a.stop = make_table(stop, dev);
   a.out_ntok = out_ntok.data_ptr<int32_t>();

@@ -112,6 +112,16 @@ enum : int {
   kFlagKeys = 1 << 10,        // CountVectorizer fit: emit a 64-bit key per kept token (no vectors)
 };
 
+// NGram stage (Spark ml.feature.NGram) between stop-word removal and the TF stage: bits 16-18 of
+// the flags word hold n - 1, so a unigram pipeline's word is what it was before the field existed.
+constexpr int kNgramShift = 16;
+constexpr int kNgramMax = 8;
+constexpr int kNgramMask = (kNgramMax - 1) << kNgramShift;
+FDX_HD int ngram_of(int flags) { return ((flags & kNgramMask) >> kNgramShift) + 1; }
+
+// Token delimiter: ' ' after cleaning (only [a-z ] survives), else Java's \s.
+FDX_HD bool is_token_delim(uint8_t c, bool cleaned) { return cleaned ? (c == ' ') : is_java_space(c); }
+
 // Status codes written per document.
 enum : int { kStatusOk = 0, kStatusTooLong = 1, kStatusNeedsHost = 2 };
 

@@ -10,6 +10,8 @@ namespace fdx {
 // terms, so doc d starting at byte s gets the slot range [s / 2 + 2 d, s / 2 + 2 d + L / 2 + 2)
 // (disjoint from its successor's: (s + L) / 2 - s / 2 >= L / 2). Capacity: bytes / 2 + 2 D + 1
 // -- half of a slot per byte (4 B of indices + 4 B of values per text byte before).
+// With an NGram stage the terms are the n-grams of the kept tokens: never more of them than kept
+// tokens (T - n + 1 <= T), so the same bound and the same slot ranges hold for every n.
 FDX_HD int64_t csr_slot(int64_t s, int64_t d) { return (s >> 1) + 2 * d; }
 FDX_HD int64_t csr_capacity(int64_t bytes, int64_t docs) { return (bytes >> 1) + 2 * docs + 1; }
 
@@ -71,6 +73,57 @@ FDX_HD int32_t table_find(const StrTable& t, uint32_t h, const uint8_t* tok, int
   return -1;
 }
 
+// ---------------------------------------------------------------- n-grams
+// The n-gram whose members are the tokens starting at starts[0 .. n) of the cleaned buffer: each
+// member runs to its delimiter (or the end of the buffer) and the members are joined by one ' ',
+// whatever delimiter separated them (Spark NGram: mkString(" ")). The members are not contiguous
+// in `clean` (removed stop words lie between them), so the joined string exists only as the
+// byte stream that `f` receives.
+template <class F>
+FDX_HD void ngram_bytes(const uint8_t* clean, int32_t nbytes, bool cleaned, const uint32_t* starts, int n, F&& f) {
+  for (int m = 0; m < n; ++m) {
+    if (m) f((uint8_t)' ');
+    for (int32_t p = (int32_t)starts[m]; p < nbytes; ++p) {
+      const uint8_t c = clean[p];
+      if (is_token_delim(c, cleaned)) break;
+      f(c);
+    }
+  }
+}
+
+// murmur3 of the joined n-gram under two seeds (the second one only feeds the 64-bit token key).
+FDX_HD uint32_t ngram_hash(const uint8_t* clean, int32_t nbytes, bool cleaned, const uint32_t* starts, int n,
+                           uint32_t seed, int32_t* len) {
+  Murmur3 m;
+  m.init(seed);
+  ngram_bytes(clean, nbytes, cleaned, starts, n, [&](uint8_t b) { m.push(b); });
+  *len = (int32_t)m.n;
+  return m.finish();
+}
+
+// table_find for an n-gram of hash `h` and joined length `len`: the candidate entry is verified
+// byte for byte against the gathered members.
+FDX_HD int32_t table_find_ngram(const StrTable& t, uint32_t h, int32_t len, const uint8_t* clean, int32_t nbytes,
+                                bool cleaned, const uint32_t* starts, int n) {
+  if (t.mask < 0) return -1;
+  uint32_t i = h & (uint32_t)t.mask;
+  for (int probe = 0; probe <= t.mask; ++probe) {
+    const int32_t e = t.slots[i];
+    if (e < 0) return -1;
+    if (t.hashes[e] == h) {
+      const int64_t o = t.offs[e];
+      if (t.offs[e + 1] - o == len) {
+        bool eq = true;
+        int32_t k = 0;
+        ngram_bytes(clean, nbytes, cleaned, starts, n, [&](uint8_t b) { eq = eq && (t.bytes[o + k] == b); ++k; });
+        if (eq) return e;
+      }
+    }
+    i = (i + 1) & (uint32_t)t.mask;
+  }
+  return -1;
+}
+
 struct FeatArgs {
   const uint8_t* text;       // padded by >= 4 bytes past the last document
   const int64_t* doc_off;    // [num_docs + 1]
@@ -88,7 +141,7 @@ struct FeatArgs {
   int32_t* out_idx;          // CSR scratch: doc d's entries at csr_slot(doc_off[d], d) (csr_slot above)
   float* out_val;
   int32_t* out_nnz;          // [num_docs]
-  int32_t* out_ntok;         // [num_docs] tokens after stop-word removal (may be null)
+  int32_t* out_ntok;         // [num_docs] tokens after stop-word removal, n-grams of them with NGram (may be null)
   double* out_raw;           // [num_docs * K] (K = trees.K, or 1 for LR)
   int32_t* out_status;       // [num_docs]
   // kFlagKeys: key of token i of doc d at out_keys[key_off[d] + i]; out_keys == nullptr -> count only

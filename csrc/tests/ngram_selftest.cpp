@@ -1,0 +1,227 @@
+// Stand-alone self-test of the n-gram mode of the fused featurizer's host twin (text_cpu.cpp) for
+// sanitizer builds: edge documents, documents with exactly k kept tokens whose n-gram members are
+// separated by removed stop words, runs of double spaces, a tab/newline document without cleaning
+// and all pairs of 1..5-letter tokens, in hashing, vocabulary and keys mode on several threads,
+// against n-grams formed as plain strings. Built with -fsanitize=address,undefined by
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_ngram_selftest(); exits non-zero on failure.
+#include <cstdio>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "ops.h"
+#include "scoring.h"
+
+using namespace fdx;
+
+static int g_fail = 0;
+#define EXPECT(c)                                                       \
+  do {                                                                  \
+    if (!(c)) { std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++g_fail; } \
+  } while (0)
+
+struct OwnedTable {
+  std::vector<int32_t> slots;
+  std::vector<uint32_t> hashes;
+  std::vector<int64_t> offs;
+  std::vector<uint8_t> bytes;
+  StrTable view() const { return StrTable{slots.data(), hashes.data(), offs.data(), bytes.data(), (int32_t)slots.size() - 1}; }
+};
+
+static uint32_t hash_of(const std::string& s, uint32_t seed) {
+  return murmur3_bytes(reinterpret_cast<const uint8_t*>(s.data()), (uint32_t)s.size(), seed);
+}
+
+static OwnedTable make_table(const std::vector<std::string>& words) {
+  OwnedTable t;
+  size_t size = 16;
+  while (size < 2 * words.size()) size <<= 1;
+  t.slots.assign(size, -1);
+  t.offs.push_back(0);
+  for (size_t i = 0; i < words.size(); ++i) {
+    const uint32_t h = hash_of(words[i], 42u);
+    t.hashes.push_back(h);
+    size_t j = h & (size - 1);
+    while (t.slots[j] >= 0) j = (j + 1) & (size - 1);
+    t.slots[j] = (int32_t)i;
+    t.bytes.insert(t.bytes.end(), words[i].begin(), words[i].end());
+    t.offs.push_back((int64_t)t.bytes.size());
+  }
+  t.bytes.push_back(0);
+  return t;
+}
+
+static bool java_space(unsigned char c) { return c == ' ' || c == '\t' || c == '\n' || c == 0x0B || c == '\f' || c == '\r'; }
+
+// scalar reference: (clean,) split with Java semantics, drop stop words, join runs of n by ' '
+static std::vector<std::string> ref_ngrams(const std::string& s, bool clean, const std::vector<std::string>& stop, int n) {
+  std::string c;
+  for (unsigned char ch : s) {
+    const unsigned char l = (ch >= 'A' && ch <= 'Z') ? ch + 32 : ch;
+    if (!clean) c.push_back((char)ch);          // the pre-lowered path passes the bytes through
+    else if ((l >= 'a' && l <= 'z') || l == ' ') c.push_back((char)l);
+  }
+  auto delim = [&](unsigned char ch) { return clean ? ch == ' ' : java_space(ch); };
+  std::vector<std::string> parts;
+  long q = -1;
+  for (long i = (long)c.size() - 1; i >= 0; --i) if (!delim((unsigned char)c[i])) { q = i; break; }
+  if (q < 0) {
+    if (c.empty()) parts.push_back("");
+  } else {
+    std::string cur;
+    for (long i = 0; i <= q; ++i) {
+      if (delim((unsigned char)c[i])) { parts.push_back(cur); cur.clear(); } else { cur.push_back(c[i]); }
+    }
+    parts.push_back(cur);
+  }
+  std::vector<std::string> kept;
+  for (auto& p : parts) {
+    bool sw = false;
+    for (auto& w : stop) sw = sw || (w == p);
+    if (!sw) kept.push_back(p);
+  }
+  std::vector<std::string> out;
+  for (size_t i = 0; i + n <= kept.size(); ++i) {
+    std::string g = kept[i];
+    for (int m = 1; m < n; ++m) g += " " + kept[i + m];
+    out.push_back(g);
+  }
+  return out;
+}
+
+static std::vector<std::string> documents(int n) {
+  std::vector<std::string> docs = {"Hi I heard about Spark", "", " ", "   ", "a", "a b", "a  b", " a b ", "a  b  c ",
+                                   "the the the", "the gift the card the", "ab c a bc a b ab c", "x  y   z    w",
+                                   "Hello World, the END is near!", "ABC d\xc3\xa9" "f 123 gift card"};
+  const int ks[] = {0, 1, n - 1, n, n + 1, 63, 64, 65, 64 + n - 1, 127, 128, 129};
+  for (int k : ks) {          // k kept tokens, every one followed by one or two stop words
+    std::string d;
+    for (int i = 0; i < k; ++i) d += "w" + std::string(1, (char)('a' + i % 26)) + std::string(i % 3, 'x') + (i % 2 ? " the " : " is a ");
+    docs.push_back(d);
+  }
+  std::vector<std::string> toks;
+  for (int len = 1; len <= 5; ++len) toks.push_back(std::string("qrstu").substr(0, len));
+  for (auto& x : toks) for (auto& y : toks) docs.push_back(x + " " + y + " " + y + "  " + x);
+  uint32_t r = 12345u;
+  for (int i = 0; i < 300; ++i) {
+    std::string d;
+    const int T = (int)((r = r * 1664525u + 1013904223u) >> 24) % 40;
+    for (int t = 0; t < T; ++t) {
+      r = r * 1664525u + 1013904223u;
+      const char* words[] = {"gift", "card", "the", "wire", "a", "transfer", "is", "verify", "", "account", "b"};
+      d += words[(r >> 20) % 11];
+      d += ((r >> 8) % 7 == 0) ? "  " : " ";
+    }
+    docs.push_back(d);
+  }
+  return docs;
+}
+
+static void run_mode(const std::vector<std::string>& docs, bool clean, bool use_stop, int n, int threads) {
+  const std::vector<std::string> stop = use_stop ? std::vector<std::string>{"the", "a", "is"} : std::vector<std::string>{};
+  OwnedTable st = make_table(stop);
+  std::vector<uint8_t> text;
+  std::vector<int64_t> off = {0};
+  for (auto& d : docs) { text.insert(text.end(), d.begin(), d.end()); off.push_back((int64_t)text.size()); }
+  text.resize(text.size() + 16, 0);
+  const int64_t D = (int64_t)docs.size();
+  const int F = 10007;
+  const int32_t ngbits = (n - 1) << kNgramShift;
+  EXPECT(ngram_of(ngbits) == n && ngram_of(0) == 1);
+
+  const int64_t cap = csr_capacity((int64_t)text.size(), D);
+  std::vector<int32_t> idx(cap), nnz(D), ntok(D), status(D, -1);
+  std::vector<float> val(cap);
+  std::vector<double> raw(D);
+  FeatArgs a{};
+  a.text = text.data();
+  a.doc_off = off.data();
+  a.num_docs = (int32_t)D;
+  a.flags = (clean ? kFlagClean : kFlagPreLowered) | (use_stop ? kFlagStopwords : 0) | kFlagWriteCsr | ngbits;
+  a.num_features = F;
+  a.stop = st.view();
+  a.vocab.mask = -1;
+  a.min_tf = 1.0;
+  a.out_idx = idx.data();
+  a.out_val = val.data();
+  a.out_nnz = nnz.data();
+  a.out_ntok = ntok.data();
+  a.out_raw = raw.data();
+  a.out_status = status.data();
+
+  // 1. hashing
+  featurize_score_cpu(a, nullptr, 0, threads);
+  for (int64_t d = 0; d < D; ++d) {
+    EXPECT(status[d] == kStatusOk);
+    const auto grams = ref_ngrams(docs[d], clean, stop, n);
+    EXPECT(ntok[d] == (int32_t)grams.size());
+    std::map<int, double> ref;
+    for (auto& g : grams) ref[non_negative_mod(hash_of(g, 42u), F)] += 1;
+    EXPECT(nnz[d] == (int32_t)ref.size());
+    EXPECT(nnz[d] <= (off[d + 1] - off[d]) / 2 + 2);
+    const int64_t base = csr_slot(off[d], d);
+    for (int32_t j = 0; j < nnz[d] && j < (int32_t)ref.size(); ++j)
+      EXPECT(ref.count(idx[base + j]) && ref[idx[base + j]] == val[base + j]);
+  }
+
+  // 2. vocabulary: entries that differ only in where the space sits, and entries absent from the text
+  const std::vector<std::string> words = {"ab c", "a bc", "a b", "gift card", "wire transfer", "q qr", "qr q", "absent term",
+                                          "abc", "", " ", "card gift card", "gift card wire", " b"};
+  OwnedTable vt = make_table(words);
+  FeatArgs v = a;
+  v.flags |= kFlagVocab;
+  v.vocab = vt.view();
+  v.num_features = (int32_t)words.size();
+  std::fill(status.begin(), status.end(), -1);
+  featurize_score_cpu(v, nullptr, 0, threads);
+  for (int64_t d = 0; d < D; ++d) {
+    EXPECT(status[d] == kStatusOk);
+    const auto grams = ref_ngrams(docs[d], clean, stop, n);
+    EXPECT(ntok[d] == (int32_t)grams.size());
+    std::map<int, double> ref;
+    for (auto& g : grams)
+      for (size_t w = 0; w < words.size(); ++w) if (words[w] == g) ref[(int)w] += 1;
+    EXPECT(nnz[d] == (int32_t)ref.size());
+    const int64_t base = csr_slot(off[d], d);
+    for (int32_t j = 0; j < nnz[d] && j < (int32_t)ref.size(); ++j)
+      EXPECT(ref.count(idx[base + j]) && ref[idx[base + j]] == val[base + j]);
+  }
+
+  // 3. keys: count pass, then key pass at the scanned offsets
+  std::vector<int32_t> kt(D), ks(D, -1);
+  FeatArgs k = a;
+  k.flags = (a.flags & ~kFlagWriteCsr) | kFlagKeys;
+  k.out_ntok = kt.data();
+  k.out_status = ks.data();
+  featurize_score_cpu(k, nullptr, 0, threads);
+  std::vector<int64_t> koff(D + 1, 0);
+  for (int64_t d = 0; d < D; ++d) koff[d + 1] = koff[d] + kt[d];
+  std::vector<uint64_t> keys(koff[D] + 1);
+  k.key_off = koff.data();
+  k.out_keys = keys.data();
+  featurize_score_cpu(k, nullptr, 0, threads);
+  for (int64_t d = 0; d < D; ++d) {
+    const auto grams = ref_ngrams(docs[d], clean, stop, n);
+    EXPECT(ks[d] == kStatusOk && kt[d] == (int32_t)grams.size());
+    for (size_t i = 0; i < grams.size() && (int64_t)i < kt[d]; ++i)
+      EXPECT(keys[koff[d] + i] == (((uint64_t)hash_of(grams[i], 42u) << 32) | hash_of(grams[i], kKeySeed2)));
+  }
+}
+
+int main() {
+  for (int n : {2, 3}) {
+    const auto docs = documents(n);
+    for (bool stop : {false, true}) run_mode(docs, true, stop, n, 4);
+    // without cleaning tabs and newlines split too, and the joiner is still ' '
+    std::vector<std::string> raw = docs;
+    raw.push_back("gift\tcard\nwire\r\ntransfer  the\x0b" "b\fend");
+    raw.push_back("\ta\n\nb\t");
+    for (bool stop : {false, true}) run_mode(raw, false, stop, n, 3);
+  }
+  if (g_fail) {
+    std::fprintf(stderr, "%d failure(s)\n", g_fail);
+    return 1;
+  }
+  std::printf("ngram selftest ok\n");
+  return 0;
+}

@@ -56,9 +56,11 @@ void process_doc(const FeatArgs& a, int32_t d, std::string& clean, std::vector<u
   const bool use_vocab = (a.flags & kFlagVocab) != 0;
   const bool use_stop = (a.flags & kFlagStopwords) != 0;
   const bool keys_mode = (a.flags & kFlagKeys) != 0;
+  const int ng = ngram_of(a.flags);
   auto emit = [&](int64_t start, int64_t len) {
     const uint32_t h = murmur3_bytes(cb + start, (uint32_t)len, 42u);
     if (use_stop && table_find(a.stop, h, cb + start, (int32_t)len) >= 0) return;
+    if (ng > 1) { toks.push_back((uint32_t)start); return; }   // n-gram mode: starts of the kept tokens
     if (keys_mode) {
       if (a.out_keys)
         a.out_keys[a.key_off[d] + nall] = ((uint64_t)h << 32) | murmur3_bytes(cb + start, (uint32_t)len, kKeySeed2);
@@ -80,6 +82,27 @@ void process_doc(const FeatArgs& a, int32_t d, std::string& clean, std::vector<u
     int64_t end = start;
     while (end < n && !delim(cb[end])) ++end;
     emit(start, end - start);
+  }
+  if (ng > 1) {
+    // the n-gram of kept tokens i .. i+ng-1 replaces start i by its bucket, compacted in place
+    // (same definition and helpers as pass 4b of the kernel)
+    const int64_t ngrams = (int64_t)toks.size() >= ng ? (int64_t)toks.size() - ng + 1 : 0;
+    size_t nk = 0;
+    for (int64_t i = 0; i < ngrams; ++i) {
+      int32_t len = 0;
+      const uint32_t h = ngram_hash(cb, (int32_t)n, cleaned, toks.data() + i, ng, 42u, &len);
+      if (keys_mode) {
+        if (a.out_keys)
+          a.out_keys[a.key_off[d] + i] =
+              ((uint64_t)h << 32) | ngram_hash(cb, (int32_t)n, cleaned, toks.data() + i, ng, kKeySeed2, &len);
+        continue;
+      }
+      const int32_t bucket = use_vocab ? table_find_ngram(a.vocab, h, len, cb, (int32_t)n, cleaned, toks.data() + i, ng)
+                                       : non_negative_mod(h, a.num_features);
+      if (bucket >= 0) toks[nk++] = (uint32_t)bucket;
+    }
+    toks.resize(nk);
+    nall = (int32_t)ngrams;
   }
   if (keys_mode) {
     if (a.out_ntok) a.out_ntok[d] = nall;

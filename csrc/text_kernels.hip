@@ -18,6 +18,11 @@
 // dialogue per single-wave workgroup, 64 KB / 16384 tokens, ~128 KB LDS -- CDNA4 lets one
 // workgroup take up to 160 KB) that runs only on the documents the first launch flags as too
 // long (long transcripts stay on the GPU). Longer ones are finished by the host.
+// With an NGram stage (n - 1 in bits 16-18 of the flags) a second set of instantiations runs: the
+// token pass keeps the start offsets of the tokens that survive stop-word removal in the token
+// table, and a pass 4b gives lane i the n-gram that starts at kept token i, hashes its members'
+// bytes joined by ' ' and writes the bucket back into the table in place. From the sort onwards
+// the two modes are the same code; the unigram instantiations compile as if the mode did not exist.
 #include "scoring.h"
 #include "ops.h"
 
@@ -78,7 +83,7 @@ __device__ __forceinline__ uint32_t hash_token(const uint8_t* s_clean, int p, in
   return m.finish();
 }
 
-template <int CAPB, int CAPT, int WAVES>
+template <int CAPB, int CAPT, int WAVES, bool NGRAM>
 __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs a) {
   static_assert(CAPB / 4 >= CAPT && CAPB <= 65536, "counts reuse the byte buffer; token starts are 16-bit");
   __shared__ __attribute__((aligned(16))) uint8_t s_clean_all[WAVES][CAPB];
@@ -172,6 +177,19 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
   const bool keys_mode = (a.flags & kFlagKeys) != 0;
   auto emit = [&](int start, bool valid) {
     int len = 0;
+    if constexpr (NGRAM) {
+      // n-gram mode: only the stop-word filter looks at single tokens; keep the survivors' starts
+      bool keep_sw = valid;
+      if (valid && use_stop) {
+        const uint32_t h = hash_token(s_clean, start, n, cleaned, &len);
+        keep_sw = table_find(a.stop, h, s_clean + start, len) < 0;
+      }
+      const unsigned long long sm = __ballot(keep_sw);
+      const int slot = ntok + popc_below(sm);
+      if (keep_sw && slot < CAPT) s_tok[slot] = (uint32_t)start;
+      ntok += __popcll(sm);
+      return;
+    }
     bool keep_sw = false;   // survived stop-word removal
     int32_t bucket = -1;
     uint32_t h = 0;
@@ -219,6 +237,45 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
       const int start = (lane < qn) ? s_q[lane] : 0;
       emit(start, lane < qn);
     }
+  }
+  if constexpr (NGRAM) {
+    // ---------------------------------------------------------------- 4b. n-grams
+    // s_tok[0 .. ntok) holds the kept tokens' starts. Lane i of a 64-wide batch owns the n-gram of
+    // kept tokens i .. i+ng-1 and replaces the starts by buckets in place: a batch reads starts at
+    // or after its base only, all its reads (the vocabulary check reads them again) come before its
+    // writes, and it writes below base + 64, where no later batch reads.
+    if (ntok > CAPT) {
+      if (lane == 0) a.out_status[d] = kStatusTooLong;
+      return;
+    }
+    lds_sync();
+    const int ng = ngram_of(a.flags);
+    const int ngrams = ntok >= ng ? ntok - ng + 1 : 0;
+    int nk = 0;
+    for (int base = 0; base < ngrams; base += kWave) {
+      const int i = base + lane;
+      int32_t bucket = -1;
+      if (i < ngrams) {
+        int32_t len = 0;
+        const uint32_t h = ngram_hash(s_clean, n, cleaned, s_tok + i, ng, 42u, &len);
+        if (keys_mode) {
+          if (a.out_keys)
+            a.out_keys[a.key_off[d] + i] =
+                ((uint64_t)h << 32) | ngram_hash(s_clean, n, cleaned, s_tok + i, ng, kKeySeed2, &len);
+        } else {
+          bucket = use_vocab ? table_find_ngram(a.vocab, h, len, s_clean, n, cleaned, s_tok + i, ng)
+                             : non_negative_mod(h, a.num_features);
+        }
+      }
+      const bool keep = bucket >= 0;
+      const unsigned long long km = __ballot(keep);
+      lds_sync();
+      if (keep) s_tok[nk + popc_below(km)] = (uint32_t)bucket;
+      nk += __popcll(km);
+      lds_sync();
+    }
+    nall = ngrams;    // CountVectorizer minTF denominator: the number of n-grams
+    ntok = nk;
   }
   if (keys_mode) {
     if (lane == 0) {
@@ -352,16 +409,22 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
   }
 }
 
-void launch_featurize_score(const FeatArgs& a, hipStream_t stream) {
+template <bool NGRAM>
+static void launch_mode(const FeatArgs& a, hipStream_t stream) {
   if (a.doc_list) {          // long dialogues: one per single-wave workgroup
     if (a.n_list > 0)
-      hipLaunchKernelGGL((featurize_score_kernel<kLongCapB, kLongCapT, 1>), dim3(a.n_list), dim3(kWave), 0, stream, a);
+      hipLaunchKernelGGL((featurize_score_kernel<kLongCapB, kLongCapT, 1, NGRAM>), dim3(a.n_list), dim3(kWave), 0,
+                         stream, a);
     return;
   }
   if (a.num_docs <= 0) return;
   const int blocks = (a.num_docs + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL((featurize_score_kernel<kCapB, kCapT, kWavesPerBlock>), dim3(blocks), dim3(kWave * kWavesPerBlock),
-                     0, stream, a);
+  hipLaunchKernelGGL((featurize_score_kernel<kCapB, kCapT, kWavesPerBlock, NGRAM>), dim3(blocks),
+                     dim3(kWave * kWavesPerBlock), 0, stream, a);
+}
+
+void launch_featurize_score(const FeatArgs& a, hipStream_t stream) {
+  if (ngram_of(a.flags) > 1) launch_mode<true>(a, stream); else launch_mode<false>(a, stream);
 }
 
 }  // namespace fdx

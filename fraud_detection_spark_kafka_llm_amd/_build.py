@@ -200,6 +200,24 @@ def build_eval_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     return out
 
 
+def build_ngram_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/ngram_selftest.cpp`` + the fused featurizer's host twin (``text_cpu.cpp``) as a
+    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
+    ``build_eval_selftest`` (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("ngram_selftest_asan" if sanitize else "ngram_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "ngram_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "text_cpu.cpp"}"\n#include "{CSRC / "tests" / "ngram_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -210,7 +228,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the TreeSHAP host twin")
     ap.add_argument("--eval-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the validation-monitoring host twins")
+    ap.add_argument("--ngram-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the n-gram mode of the featurizer's host twin")
     args = ap.parse_args(argv)
+    if args.ngram_selftest:
+        return subprocess.run([str(build_ngram_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.host_selftest or args.contrib_selftest or args.eval_selftest:
         exe = build_host_selftest() if args.host_selftest else \
             (build_contrib_selftest() if args.contrib_selftest else build_eval_selftest())

@@ -1,6 +1,6 @@
-"""Feature stages: Tokenizer, StopWordsRemover, HashingTF, CountVectorizer(+Model), IDF(+Model).
+"""Feature stages: Tokenizer, StopWordsRemover, NGram, HashingTF, CountVectorizer(+Model), IDF(+Model).
 
-Tokenizer/StopWordsRemover only record lineage (``TokenColumn``); HashingTF and CountVectorizerModel
+Tokenizer/StopWordsRemover/NGram only record lineage (``TokenColumn``); HashingTF and CountVectorizerModel
 consume it through the fused native featurizer (one gfx950 launch: clean -> split -> stop words ->
 murmur3/vocab -> sparse vector), so token lists are never materialised on the hot path.
 Reference usage: /root/reference/fraud_detection_spark.py:47-54 and shipped stages 0-3
@@ -16,7 +16,7 @@ import torch
 
 from ..io import spark_format as sf
 from ..ops import oracle
-from ..ops.text import FeatureSpec, featurize_score
+from ..ops.text import NGRAM_MAX, FeatureSpec, featurize_score
 from ..utils.config import default_device
 from .base import Estimator, HasInOut, Model, Param, Transformer, register
 from .frame import Frame, TextColumn, TokenColumn
@@ -39,7 +39,7 @@ def _tokens_of(col) -> list:
 def native_vectors(col: TokenColumn, spec_kw: dict, device=None) -> VectorColumn:
     """Run the fused native featurizer over a fusable token lineage."""
     raw, clean = col.text.lineage()
-    spec = FeatureSpec(clean=clean, stopwords=col.stopwords, **spec_kw)
+    spec = FeatureSpec(clean=clean, stopwords=col.stopwords, ngram=col.ngram, **spec_kw)
     dev = torch.device(device) if device is not None else default_device()
     res = featurize_score(raw.packed(), spec, want_csr=True, device=dev)
     indptr, idx, val = res.csr()
@@ -76,11 +76,37 @@ class StopWordsRemover(HasInOut, Transformer):
         col = frame.column(self.getInputCol())
         sw = tuple(self.getStopWords())
         cs = bool(self.getCaseSensitive())
-        if isinstance(col, TokenColumn) and col.fusable and col.stopwords is None and not cs:
+        if isinstance(col, TokenColumn) and col.fusable and col.stopwords is None and col.ngram == 1 and not cs:
             return frame.withColumn(self.getOutputCol(), TokenColumn(col.text, sw, cs))
         toks = [oracle.remove_stopwords(t, sw, cs) for t in _tokens_of(col)]
         text = col.text if isinstance(col, TokenColumn) else TextColumn([""] * len(toks))
         return frame.withColumn(self.getOutputCol(), TokenColumn(text, sw, cs, toks))
+
+
+@register("org.apache.spark.ml.feature.NGram")
+class NGram(HasInOut, Transformer):
+    """Runs of ``n`` consecutive input tokens joined by one space (``oracle.ngrams``). Over a
+    fusable token lineage with ``n <= NGRAM_MAX`` the stage only records ``n``, and the TF stage
+    forms the n-grams inside the fused kernel; otherwise it runs on the host."""
+    _uid_prefix = "NGram"
+    _params = [Param("n", "number of tokens in each n-gram (>= 1)", 2, int)]
+
+    def _default_hook(self) -> None:
+        self._defaultParamMap = {"outputCol": f"{self.uid}__output", "n": 2}
+
+    def set(self, name: str, value):
+        if name == "n" and value is not None and int(value) < 1:
+            raise ValueError(f"NGram n must be >= 1, got {value}")
+        return super().set(name, value)
+
+    def _transform(self, frame: Frame) -> Frame:
+        col = frame.column(self.getInputCol())
+        n = int(self.getN())
+        if isinstance(col, TokenColumn) and col.fusable and col.ngram == 1 and n <= NGRAM_MAX:
+            return frame.withColumn(self.getOutputCol(), TokenColumn(col.text, col.stopwords, ngram=n))
+        toks = [oracle.ngrams(t, n) for t in _tokens_of(col)]
+        text = col.text if isinstance(col, TokenColumn) else TextColumn([""] * len(toks))
+        return frame.withColumn(self.getOutputCol(), TokenColumn(text, tokens=toks))
 
 
 @register("org.apache.spark.ml.feature.HashingTF")
@@ -168,14 +194,15 @@ def _df_bounds(min_df: float, max_df: float, n_docs: int) -> tuple:
 def cv_fit_native(col: TokenColumn, vocab_size: int, min_df: float = 1.0, max_df: float = float(2 ** 63 - 1),
                   device=None) -> list:
     """CountVectorizer fit on the device (K-05, X-05): the fused text kernel emits a 64-bit key per
-    kept token, a device sort yields corpus term counts and document frequencies, the minDF/maxDF
-    filter and the top-``vocab_size`` selection run on device; only the selected terms are turned
+    kept token (per n-gram of them over an NGram lineage), a device sort yields corpus term counts
+    and document frequencies, the minDF/maxDF filter and the top-``vocab_size`` selection run on
+    device; only the selected terms (tokens, or n-grams joined by a space) are turned
     back into strings, from the first document containing each (host re-tokenisation of those
     documents only). Ordering: count descending, ties by term (same as the host fit)."""
     from ..ops.text import term_doc_counts, token_key, token_keys
 
     raw, clean = col.text.lineage()
-    spec = FeatureSpec(clean=clean, stopwords=col.stopwords, num_features=1)
+    spec = FeatureSpec(clean=clean, stopwords=col.stopwords, num_features=1, ngram=col.ngram)
     dev = torch.device(device) if device is not None else default_device()
     keys, ntok = token_keys(raw.packed(), spec, dev)
     uk, tf, df, first = term_doc_counts(keys, ntok)
@@ -194,7 +221,7 @@ def cv_fit_native(col: TokenColumn, vocab_size: int, min_df: float = 1.0, max_df
         toks = oracle.tokenize(oracle.clean_text(s) if clean else s)
         if col.stopwords is not None:
             toks = oracle.remove_stopwords(toks, col.stopwords)
-        for t in toks:
+        for t in oracle.ngrams(toks, col.ngram):
             k = token_key(t)
             if k in want and want[k] is None:
                 want[k] = t

@@ -5,8 +5,8 @@ Columns are typed containers rather than Python rows:
 * ``TextColumn``  — strings, packed lazily into one UTF-8 buffer (``PackedText``) for the native
   featurizer; a cleaned column remembers its raw source (``lineage``) so the native kernel can
   apply ``regexp_replace(lower(x), "[^a-zA-Z ]", "")`` itself;
-* ``TokenColumn`` — the *lineage* of Tokenizer/StopWordsRemover output (source text + stop
-  words); token lists are only materialised if someone reads them, while HashingTF /
+* ``TokenColumn`` — the *lineage* of Tokenizer/StopWordsRemover/NGram output (source text + stop
+  words + n-gram width); token lists are only materialised if someone reads them, while HashingTF /
   CountVectorizer consume the lineage through the fused native op;
 * ``VectorColumn`` (``ml.linalg``) — CSR or dense torch tensors on a device;
 * numpy / torch arrays for scalars and ``[N, K]`` vector-valued outputs (``probability``);
@@ -74,10 +74,11 @@ class TextColumn:
 
 class TokenColumn:
     def __init__(self, text: TextColumn, stopwords: Optional[tuple] = None, case_sensitive: bool = False,
-                 tokens: Optional[list] = None):
+                 tokens: Optional[list] = None, ngram: int = 1):
         self.text = text
         self.stopwords = stopwords
         self.case_sensitive = case_sensitive
+        self.ngram = int(ngram)       # NGram.n applied after the stop-word removal (1: none)
         self._tokens = tokens
 
     @property
@@ -90,6 +91,8 @@ class TokenColumn:
             toks = [oracle.tokenize(s or "") for s in self.text.strings]
             if self.stopwords is not None:
                 toks = [oracle.remove_stopwords(t, self.stopwords, self.case_sensitive) for t in toks]
+            if self.ngram > 1:
+                toks = [oracle.ngrams(t, self.ngram) for t in toks]
             self._tokens = toks
         return self._tokens
 
@@ -99,8 +102,8 @@ class TokenColumn:
     def take(self, rows: np.ndarray) -> "TokenColumn":
         if self._tokens is not None:
             return TokenColumn(self.text.take(rows), self.stopwords, self.case_sensitive,
-                               [self._tokens[i] for i in rows])
-        return TokenColumn(self.text.take(rows), self.stopwords, self.case_sensitive)
+                               [self._tokens[i] for i in rows], self.ngram)
+        return TokenColumn(self.text.take(rows), self.stopwords, self.case_sensitive, ngram=self.ngram)
 
 
 class Lazy:

@@ -1,6 +1,6 @@
 """Fusion of a text pipeline's stages into one native launch.
 
-``Tokenizer -> [StopWordsRemover] -> HashingTF|CountVectorizerModel -> [IDFModel] -> [classifier]``
+``Tokenizer -> [StopWordsRemover] -> [NGram] -> HashingTF|CountVectorizerModel -> [IDFModel] -> [classifier]``
 (the shape of both the shipped ``dialogue_classification_model`` and the trainer's pipelines,
 /root/reference/fraud_detection_spark.py:47-91) runs as ONE ``featurize_score`` call: raw UTF-8
 bytes in, fp64 scores out. Intermediate columns (``words``, ``filtered_words``,
@@ -12,10 +12,10 @@ from typing import Optional, Sequence
 
 import torch
 
-from ..ops.text import FeatureSpec, PackedText, featurize_score
+from ..ops.text import NGRAM_MAX, FeatureSpec, PackedText, featurize_score
 from ..utils.config import default_device
 from .classification import ClassificationModelBase
-from .feature import CountVectorizerModel, HashingTF, IDFModel, StopWordsRemover, Tokenizer, native_vectors
+from .feature import CountVectorizerModel, HashingTF, IDFModel, NGram, StopWordsRemover, Tokenizer, native_vectors
 from .frame import Frame, Lazy, TextColumn, TokenColumn
 from .linalg import VectorColumn
 
@@ -24,13 +24,14 @@ class FusedPipeline:
     """Compiled text->score chain. ``predict`` returns (prediction, probability, rawPrediction)."""
 
     def __init__(self, tokenizer: Tokenizer, remover: Optional[StopWordsRemover], tf, idf: Optional[IDFModel],
-                 model: Optional[ClassificationModelBase], device=None):
+                 model: Optional[ClassificationModelBase], ngram: Optional[NGram] = None, device=None):
         self.tokenizer, self.remover, self.tf, self.idf, self.model = tokenizer, remover, tf, idf, model
+        self.ngram = int(ngram.getN()) if ngram is not None else 1
         self.device = torch.device(device) if device is not None else default_device()
         kw = tf.spec_kwargs()
         self.stopwords = tuple(remover.getStopWords()) if remover is not None else None
-        self._spec_raw = FeatureSpec(clean=False, stopwords=self.stopwords, **kw)
-        self._spec_clean = FeatureSpec(clean=True, stopwords=self.stopwords, **kw)
+        self._spec_raw = FeatureSpec(clean=False, stopwords=self.stopwords, ngram=self.ngram, **kw)
+        self._spec_clean = FeatureSpec(clean=True, stopwords=self.stopwords, ngram=self.ngram, **kw)
         self.dim = self._spec_raw.dim
         if idf is not None and idf.idf.size < self.dim:
             raise ValueError("IDF vector is shorter than the TF feature space")
@@ -44,7 +45,7 @@ class FusedPipeline:
         chain = match_chain(stages)
         if chain is None or chain[-1] != len(stages):
             raise ValueError("pipeline is not a fusable text->classifier chain")
-        return cls(*chain[:5], device=device)
+        return cls(*chain[:6], device=device)
 
     def spec(self, clean: bool) -> FeatureSpec:
         return self._spec_clean if clean else self._spec_raw
@@ -76,7 +77,7 @@ class FusedPipeline:
 
 
 def match_chain(stages: Sequence):
-    """Return (tokenizer, remover, tf, idf, model, n_stages_covered) or None."""
+    """Return (tokenizer, remover, tf, idf, model, ngram, n_stages_covered) or None."""
     if not stages or not isinstance(stages[0], Tokenizer):
         return None
     i = 1
@@ -87,6 +88,12 @@ def match_chain(stages: Sequence):
         if r.getInputCol() != cur or r.getCaseSensitive():
             return None
         remover, cur, i = r, r.getOutputCol(), i + 1
+    ngram = None
+    if i < len(stages) and isinstance(stages[i], NGram):
+        g = stages[i]
+        if g.getInputCol() != cur or not 1 <= int(g.getN()) <= NGRAM_MAX:
+            return None
+        ngram, cur, i = g, g.getOutputCol(), i + 1
     if i >= len(stages) or not isinstance(stages[i], (HashingTF, CountVectorizerModel)):
         return None
     tf = stages[i]
@@ -99,7 +106,7 @@ def match_chain(stages: Sequence):
     model = None
     if i < len(stages) and isinstance(stages[i], ClassificationModelBase) and stages[i].getFeaturesCol() == cur:
         model, i = stages[i], i + 1
-    return tokenizer_tuple(stages[0], remover, tf, idf, model, i)
+    return tokenizer_tuple(stages[0], remover, tf, idf, model, ngram, i)
 
 
 def tokenizer_tuple(*a):
@@ -108,7 +115,7 @@ def tokenizer_tuple(*a):
 
 class _Plan:
     def __init__(self, chain, frame: Frame):
-        self.tok, self.rem, self.tf, self.idf, self.model, self.n = chain
+        self.tok, self.rem, self.tf, self.idf, self.model, self.ngram, self.n = chain
 
     def run(self, frame: Frame, rest: Sequence = ()) -> Frame:
         tok, rem, tf, idf, model = self.tok, self.rem, self.tf, self.idf, self.model
@@ -122,6 +129,9 @@ class _Plan:
         if rem is not None:
             tokens = TokenColumn(text, tuple(rem.getStopWords()))
             frame = frame.withColumn(rem.getOutputCol(), tokens)
+        if self.ngram is not None:
+            tokens = TokenColumn(text, tokens.stopwords, ngram=int(self.ngram.getN()))
+            frame = frame.withColumn(self.ngram.getOutputCol(), tokens)
         tf_col = Lazy(lambda: native_vectors(tokens, tf.spec_kwargs()), n)
         frame = frame.withColumn(tf.getOutputCol(), tf_col)
         if idf is not None:
@@ -132,7 +142,7 @@ class _Plan:
                 return VectorColumn.scaled_counts(vc.size, ip, ix, v, w)
             frame = frame.withColumn(idf.getOutputCol(), Lazy(_idf, n))
         if model is not None:
-            fp = FusedPipeline(tok, rem, tf, idf, model)
+            fp = FusedPipeline(tok, rem, tf, idf, model, self.ngram)
             res = fp.run(raw.packed(), clean=clean)
             frame = model.attach_outputs(frame, res.raw)
         for s in rest:

@@ -14,6 +14,10 @@ long-dialogue kernel straight from the device copy of the text (no host re-pack)
 scored by the same native CSR scorer whose lane-strided order equals the fused kernel's, so the
 result is bitwise equal to the host featurizer's whole-dialogue result. Dialogues without a
 valid cut inside a window (one "word" longer than a segment) are left to the host path.
+
+With an NGram stage (``spec.ngram > 1``) the terms are runs of consecutive tokens, and a run can
+span a cut, so the segments' counts no longer add up to the dialogue's: ``featurize_long`` declines
+every dialogue then (``done = False``) and they finish on the host path.
 """
 from __future__ import annotations
 
@@ -61,7 +65,7 @@ def featurize_long(data_dev: torch.Tensor, host_buf: np.ndarray, doc_off: np.nda
 
     C = native.lib()
     bounds, seg_doc, done = [], [], np.zeros(len(docs), dtype=bool)
-    for j, d in enumerate(docs):
+    for j, d in enumerate(docs if spec.ngram == 1 else ()):   # an n-gram can span a cut: host path
         b = split_points(host_buf, int(doc_off[d]), int(doc_off[d + 1]))
         if b is None:
             continue

@@ -7,6 +7,7 @@ native CPU path and the gfx950 kernels:
 * ``clean_text``      — ``regexp_replace(lower(dialogue), "[^a-zA-Z ]", "")``
                         (/root/reference/fraud_detection_spark.py:42-45, utils/agent_api.py:139-145)
 * ``java_split_ws``   — ``Tokenizer``: ``lower().split("\\\\s")`` with Java split semantics
+* ``ngrams``          — ``NGram``: runs of ``n`` consecutive tokens joined by one space
 * ``murmur3_x86_32``  — Spark ``Murmur3_x86_32.hashUnsafeBytes2`` (HashingTF, seed 42)
 * ``hashing_tf``      — ``nonNegativeMod(hash, numFeatures)`` term counts
 * ``idf_fit``         — ``ln((N + 1) / (df + 1))``, zeroed below ``minDocFreq``
@@ -56,6 +57,15 @@ def remove_stopwords(tokens: Sequence[str], stopwords: Iterable[str], case_sensi
         return [t for t in tokens if t not in sw]
     sw = {w.lower() for w in stopwords}
     return [t for t in tokens if t.lower() not in sw]
+
+
+def ngrams(tokens: Sequence[str], n: int) -> list[str]:
+    """Spark ``NGram``: every run of ``n`` consecutive tokens joined by one space, in order
+    (``tokens.sliding(n).withFilter(_.size == n).map(_.mkString(" "))``); fewer than ``n`` tokens
+    give ``[]``, empty tokens are tokens, and ``n = 1`` is the identity."""
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    return [" ".join(tokens[i:i + n]) for i in range(len(tokens) - n + 1)]
 
 
 def _rotl(x: int, r: int) -> int:

@@ -5,6 +5,7 @@
 native launch (``csrc/text_kernels.hip`` on gfx950, ``csrc/text_cpu.cpp`` on the host). The rare
 documents the GPU kernel cannot hold in LDS (longer than 4 KiB, > 1024 kept tokens) or that need
 full Unicode lowercasing are finished by the host path and patched into the device outputs.
+An optional NGram stage (``FeatureSpec.ngram``, up to ``NGRAM_MAX``) rides in the flags word.
 
 Reference semantics: SURVEY.md Appendix A.1-A.5; /root/reference/fraud_detection_spark.py:47-54
 (feature stages) and the shipped dialogue_classification_model stages 0-4.
@@ -31,6 +32,8 @@ FLAG_VOCAB = 1 << 6
 FLAG_STOPWORDS = 1 << 7
 FLAG_CMP_LESS = 1 << 8
 FLAG_PRELOWERED = 1 << 9
+NGRAM_SHIFT = 16         # bits 16-18 of the flags word: NGram width - 1 (0 for a unigram pipeline)
+NGRAM_MAX = 8            # widest n-gram the fused kernel takes; wider ones run on the host stages
 STATUS_OK, STATUS_TOO_LONG, STATUS_NEEDS_HOST = 0, 1, 2
 PAD = 16
 
@@ -157,7 +160,12 @@ class FeatureSpec:
     binary: bool = False
     vocab: Optional[Sequence[str]] = None    # CountVectorizerModel vocabulary (replaces hashing)
     min_tf: float = 1.0
+    ngram: int = 1                           # NGram.n between the remover and the TF stage (1: none)
     _tables: dict = field(default_factory=dict, repr=False, compare=False)
+
+    def __post_init__(self):
+        if not 1 <= int(self.ngram) <= NGRAM_MAX:
+            raise ValueError(f"ngram must be in [1, {NGRAM_MAX}]")
 
     @property
     def dim(self) -> int:
@@ -360,7 +368,11 @@ def _flags(spec: FeatureSpec, idf, lr, trees, want_csr: bool) -> int:
         f |= FLAG_VOCAB
     if spec.stopwords:
         f |= FLAG_STOPWORDS
-    return f
+    return f | _ngram_bits(spec)
+
+
+def _ngram_bits(spec: FeatureSpec) -> int:
+    return (int(spec.ngram) - 1) << NGRAM_SHIFT
 
 
 def csr_capacity(nbytes: int, docs: int) -> int:
@@ -513,13 +525,14 @@ def _finish_on_host(res: FeatureResult, text: PackedText, bad: np.ndarray, spec,
 
 # ------------------------------------------------------------------ CountVectorizer fit (K-05)
 def _text_flags(spec: FeatureSpec) -> int:
-    return (FLAG_CLEAN if spec.clean else 0) | (FLAG_STOPWORDS if spec.stopwords else 0)
+    return (FLAG_CLEAN if spec.clean else 0) | (FLAG_STOPWORDS if spec.stopwords else 0) | _ngram_bits(spec)
 
 
 def token_keys(text: PackedText, spec: FeatureSpec, device=None) -> tuple:
     """64-bit key of every token kept by clean -> tokenize -> stop-word removal, in document order:
     (keys int64 [T], ntok int64 [D]) on ``device``. Key = murmur3_x86_32(token, 42) << 32 |
-    murmur3_x86_32(token, 0x9747b28c). Two passes of the fused text kernel (count, then write at
+    murmur3_x86_32(token, 0x9747b28c). With ``spec.ngram > 1`` the terms are the n-grams of the
+    kept tokens (joined by one space) and ``ntok`` counts them. Two passes of the fused text kernel (count, then write at
     the scanned offsets); documents the device path flags (too long / non-ASCII without cleaning)
     are redone on the host path."""
     C = native.lib()

@@ -115,7 +115,8 @@ class ClassificationAgent:
         ``contributions``: TreeSHAP for tree models, ``w_f * x_f`` for logistic regression), by
         descending ``|contribution|``, ties by feature index. Only features present in the
         dialogue are listed. CountVectorizer features name their vocabulary word; HashingTF
-        buckets name the dialogue's own filtered tokens that hash there, joined with ``/``."""
+        buckets name the dialogue's own filtered tokens (its n-grams behind an NGram stage) that
+        hash there, joined with ``/``."""
         from ..ml.feature import CountVectorizerModel
         from ..ops import oracle
 
@@ -135,6 +136,7 @@ class ClassificationAgent:
             toks = oracle.tokenize(oracle.clean_text(dialogue))
             if fp.stopwords is not None:
                 toks = oracle.remove_stopwords(toks, fp.stopwords)
+            toks = oracle.ngrams(toks, fp.ngram)      # an NGram pipeline's terms are the n-grams
             buckets: dict = {}
             for t in dict.fromkeys(toks):
                 buckets.setdefault(oracle.term_index(t, fp.dim), []).append(t)

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from .data import synth
-from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, Pipeline, PipelineModel, RandomForestClassifier,
-                 StopWordsRemover, TextColumn, Tokenizer)
+from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, NGram, Pipeline, PipelineModel,
+                 RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
 from .ml.evaluation import evaluate_all
 from .ml.xgboost import SparkXGBClassifier
 from .ops.sparse import term_presence_by_label
@@ -71,11 +71,17 @@ def load_and_clean_data(spark: SparkSession, url: Optional[str] = DATA_URL, synt
     return df.take_rows(np.nonzero(nonempty)[0])
 
 
-def build_feature_pipeline(vocab_size: int = 20000) -> list:
-    return [Tokenizer(inputCol="clean_text", outputCol="words"),
-            StopWordsRemover(inputCol="words", outputCol="filtered_words"),
-            CountVectorizer(inputCol="filtered_words", outputCol="raw_features", vocabSize=vocab_size),
-            IDF(inputCol="raw_features", outputCol="features")]
+def build_feature_pipeline(vocab_size: int = 20000, ngram: int = 1) -> list:
+    """The reference's feature stages; ``ngram > 1`` inserts an NGram stage after the remover, so
+    the vocabulary holds phrases of ``ngram`` words instead of single words."""
+    stages = [Tokenizer(inputCol="clean_text", outputCol="words"),
+              StopWordsRemover(inputCol="words", outputCol="filtered_words")]
+    terms = "filtered_words"
+    if ngram > 1:
+        stages.append(NGram(n=ngram, inputCol=terms, outputCol="ngrams"))
+        terms = "ngrams"
+    return stages + [CountVectorizer(inputCol=terms, outputCol="raw_features", vocabSize=vocab_size),
+                     IDF(inputCol="raw_features", outputCol="features")]
 
 
 def make_classifiers(num_trees: int = 100, max_depth: int = 5, seed: int = 42) -> dict:
@@ -169,6 +175,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--model-path", default="fraud_detection_model")
     ap.add_argument("--no-plots", action="store_true")
+    ap.add_argument("--ngram", type=int, default=1, help="insert an NGram(n) stage after the stop-word remover")
     Config.add_cli_args(ap)          # --num-trees, --max-depth, --vocab-size, --seed, --device, --config ...
     args = ap.parse_args(argv)
     cfg = Config.from_cli(args)
@@ -184,7 +191,7 @@ def main(argv=None) -> dict:
         print(f"Training: {train_df.count()}")
         print(f"Validation: {val_df.count()}")
         print(f"Test: {test_df.count()}")
-        models = train_models(train_df, build_feature_pipeline(args.vocab_size),
+        models = train_models(train_df, build_feature_pipeline(args.vocab_size, args.ngram),
                               make_classifiers(args.num_trees, args.max_depth, args.seed))
         results = {name: evaluate_model(m, {"Validation": val_df, "Test": test_df}) for name, m in models.items()}
         print("\nModel Evaluation Results:")
