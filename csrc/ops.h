@@ -69,6 +69,20 @@ void launch_eval_auc(const double* margin, const float* label, int64_t n, const 
                      hipStream_t stream);
 void eval_auc_cpu(const double* margin, const float* label, int64_t n, int64_t* out);
 
+// ---------------------------------------------------------------- elastic-net LR (lr_kernels.hip / lr_cpu.cpp)
+template <class V> struct LrForwardArgs;   // lr.h
+struct LrReduceArgs;
+struct LrStepArgs;
+struct LrGradArgs;
+template <class V> void launch_lr_forward(const LrForwardArgs<V>& a, hipStream_t stream);
+template <class V> void lr_forward_cpu(const LrForwardArgs<V>& a, int threads);
+void launch_lr_reduce(const LrReduceArgs& a, hipStream_t stream);
+void lr_reduce_cpu(const LrReduceArgs& a);
+void launch_lr_owlqn_step(const LrStepArgs& a, hipStream_t stream);
+void lr_owlqn_step_cpu(const LrStepArgs& a, int threads);
+void launch_lr_pseudo_grad(const LrGradArgs& a, hipStream_t stream);
+void lr_pseudo_grad_cpu(const LrGradArgs& a, int threads);
+
 // ---------------------------------------------------------------- feature-major order (sort_kernels.hip)
 template <class V>
 struct FeatureOrderArgs {

@@ -218,6 +218,26 @@ def build_ngram_selftest(sanitize: bool = True, out: Path | None = None) -> Path
     return out
 
 
+def build_lr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/lr_selftest.cpp`` + the elastic-net logistic-regression host twins (``lr_cpu.cpp``, and
+    ``sparse_cpu.cpp`` for the SpMV the margins must equal) as a standalone executable under
+    AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_eval_selftest`` (host code only,
+    one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("lr_selftest_asan" if sanitize else "lr_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "lr_selftest_unity.cpp"
+    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in ("sparse_cpu.cpp", "lr_cpu.cpp"))
+                     + f'#include "{CSRC / "tests" / "lr_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -230,7 +250,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the validation-monitoring host twins")
     ap.add_argument("--ngram-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the n-gram mode of the featurizer's host twin")
+    ap.add_argument("--lr-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the elastic-net logistic-regression host twins")
     args = ap.parse_args(argv)
+    if args.lr_selftest:
+        return subprocess.run([str(build_lr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.ngram_selftest:
         return subprocess.run([str(build_ngram_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.host_selftest or args.contrib_selftest or args.eval_selftest:

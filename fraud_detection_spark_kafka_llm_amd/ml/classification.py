@@ -149,6 +149,8 @@ class LogisticRegression(_LRParams, Estimator):
     def _fit(self, frame: Frame) -> "LogisticRegressionModel":
         from ..models.lr import train_logistic_regression
 
+        if self.getOrDefault("family") == "multinomial":
+            raise NotImplementedError("multinomial logistic regression is not supported")
         vc = frame.column(self.getFeaturesCol())
         y = frame.column(self.getLabelCol())
         w = frame.column(self.getWeightCol()) if self.isSet("weightCol") else None

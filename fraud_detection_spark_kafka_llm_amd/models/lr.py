@@ -13,6 +13,11 @@ the gradient ``X^T r`` as the same row-wise SpMV over ``X^T`` (built once per fi
 of the entries by feature): every output is one fixed-order lane-strided dot product, no atomics,
 so repeated fits are bitwise identical on the GPU. Under data parallelism each rank holds a row
 shard and the gradient / loss / weight sums are all-reduced once per function evaluation (PAR-04).
+
+With ``regParam > 0`` and ``elasticNetParam > 0`` the objective gains the L1 term
+``regParam * (alpha * ||beta||_1 + (1 - alpha)/2 * ||beta||^2)`` and the trainer is OWL-QN (``_train_owlqn``)
+on the fused kernels of ``csrc/lr_kernels.hip``: coefficients that leave their orthant are exactly 0.0.
+Every other parameter pair runs the L-BFGS body below unchanged.
 """
 from __future__ import annotations
 
@@ -23,7 +28,8 @@ import numpy as np
 import torch
 
 from ..ml.linalg import VectorColumn
-from ..ops.sparse import spmv
+from ..ops import native
+from ..ops.sparse import lr_forward, lr_owlqn_step, lr_pseudo_grad, spmv
 from ..parallel.dist import Collectives
 from ..utils.config import default_device
 
@@ -43,8 +49,10 @@ def transpose_csr(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, nu
 def train_logistic_regression(features, labels, weights=None, max_iter: int = 100, tol: float = 1e-6,
                               reg_param: float = 0.0, elastic_net: float = 0.0, fit_intercept: bool = True,
                               standardization: bool = True, device=None, history_size: int = 10):
-    if reg_param > 0 and elastic_net > 0:
-        raise NotImplementedError("L1/elastic-net (OWL-QN) is not supported; use elasticNetParam=0")
+    if not 0.0 <= elastic_net <= 1.0:
+        raise ValueError(f"elastic_net must be in [0, 1], got {elastic_net}")
+    if reg_param < 0:
+        raise ValueError(f"reg_param must be >= 0, got {reg_param}")
     dev = torch.device(device) if device is not None else default_device()
     vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
     vc = vc.to(dev)
@@ -94,6 +102,10 @@ def train_logistic_regression(features, labels, weights=None, max_iter: int = 10
         p = float(coll.sum((w * y).sum().reshape(1))[0]) / wsum
         if 0 < p < 1:
             theta[F] = math.log(p / (1 - p))
+    if reg_param > 0 and elastic_net > 0:
+        return _train_owlqn((indptr, idx, val), (t_indptr, t_idx, t_val), y, w, wsum, scale, theta, coll,
+                            reg_param * elastic_net, reg_param * (1.0 - elastic_net), max_iter, tol, fit_intercept,
+                            history_size)
     loss, g = fg(theta)
     history = [loss]
     S, Y = [], []
@@ -144,4 +156,128 @@ def train_logistic_regression(features, labels, weights=None, max_iter: int = 10
             break
     coef = (scale * theta[:F]).cpu().numpy()
     intercept = float(theta[F]) if fit_intercept else 0.0
+    return coef, intercept, history
+
+
+# counters of the last OWL-QN fit (evaluations = line-search trials + 1, host reads, iterations):
+# read by the profile note and the micro-benchmark, never by the trainer itself
+OWLQN_STATS = {"evaluations": 0, "host_reads": 0, "iterations": 0}
+
+
+class OwlqnEvaluation:
+    """One function evaluation of the elastic-net objective on a row shard, all on the device:
+    ``lr_owlqn_step`` (trial point ``pi(x + t d; xi)``, its norms and ``pg . (x_new - x)``),
+    ``lr_forward`` (residuals, loss and residual sums), the transposed SpMV, one ``coll.sum`` of
+    ``[loss, sum r, X^T r]`` and ``lr_pseudo_grad``."""
+
+    def __init__(self, csr, t_csr, y, w, wsum, scale, coll, l1, l2, fit_intercept):
+        self.csr, self.t_csr, self.y, self.w, self.wsum, self.scale, self.coll = csr, t_csr, y, w, wsum, scale, coll
+        self.l1, self.l2, self.fit_intercept = l1, l2, fit_intercept
+
+    def __call__(self, x, d, xi, pg, t: float):
+        """Returns ``(x_new, xs_new, g, pg_new, xi_new, |pg_new|^2)`` and the device tuple
+        ``[objective, pg . (x_new - x), |pg_new|^2]`` the line search reads."""
+        F = self.scale.numel()
+        x_new, xs_new, norms = lr_owlqn_step(x, d, xi, pg, self.scale, t)
+        parts = torch.empty(F + 2, dtype=torch.float64, device=x.device)
+        r, _ = lr_forward(*self.csr, xs_new, x_new[F:], self.y, self.w, out=parts[:2])
+        native.lib().spmv(*self.t_csr, r, parts[2:], 0)
+        parts = self.coll.sum(parts)
+        g, pg_new, xi_new, pgn2 = lr_pseudo_grad(parts, self.scale, x_new, self.wsum, self.l1, self.l2,
+                                                 self.fit_intercept)
+        obj = parts[0] / self.wsum + (0.5 * self.l2) * norms[1] + self.l1 * norms[0]
+        return (x_new, xs_new, g, pg_new, xi_new, pgn2), torch.stack([obj, norms[2], pgn2[0]])
+
+
+def _train_owlqn(csr, t_csr, y, w, wsum, scale, theta, coll, l1, l2, max_iter, tol, fit_intercept, history_size):
+    """OWL-QN (Andrew & Gao 2007) on ``mean log-loss + l2/2 |beta|^2 + l1 |beta|_1`` over the coefficients
+    ``theta[:F]`` the optimiser sees (``scale`` maps them to raw-feature coefficients); ``theta[F]`` is
+    the unpenalised intercept. The two-loop recursion runs on 0-dim device tensors; the host reads
+    one tuple per line-search trial (objective, ``pg . (x_new - x)``, ``|pg|^2``) and one per iteration
+    (``s . y``)."""
+    dev = theta.device
+    F = theta.numel() - 1
+    evaluation = OwlqnEvaluation(csr, t_csr, y, w, wsum, scale, coll, l1, l2, fit_intercept)
+    pinned = torch.empty(3, dtype=torch.float64, pin_memory=dev.type == "cuda")
+    stats = OWLQN_STATS
+    stats.update(evaluations=0, host_reads=0, iterations=0)
+
+    def read(values: torch.Tensor) -> list:
+        stats["host_reads"] += 1
+        if dev.type != "cuda":
+            return values.tolist()
+        pinned[:values.numel()].copy_(values, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return pinned[:values.numel()].tolist()
+
+    def evaluate(x, d, xi, pg, t):
+        stats["evaluations"] += 1
+        state, packed = evaluation(x, d, xi, pg, t)
+        f, dec, gn2 = read(packed)
+        return state, f, dec, gn2
+
+    penalised = torch.ones(F + 1, dtype=torch.bool, device=dev)
+    penalised[F] = False
+
+    def aligned(d, pg):     # coefficients move only against their pseudo-gradient
+        return torch.where(penalised & (d * pg >= 0), torch.zeros_like(d), d)
+
+    zero = torch.zeros_like(theta)
+    # x0 has no non-zero coefficient, so the projection onto the orthant xi = 0 leaves it as it is
+    (x, xs, g, pg, xi, pgn2), f, _, gn2 = evaluate(theta, zero, zero, zero, 0.0)
+    history = [f]
+    S, Y, RHO = [], [], []
+    gamma = None
+    for _ in range(max_iter):
+        if math.sqrt(gn2) < 1e-9:
+            break
+        stats["iterations"] += 1
+        q = pg.clone()
+        alphas = []
+        for s, yv, rho in zip(reversed(S), reversed(Y), reversed(RHO)):
+            a = rho * torch.dot(s, q)
+            alphas.append(a)
+            q.addcmul_(yv, a, value=-1.0)
+        if S:
+            q *= gamma
+        else:
+            q *= 1.0 / torch.clamp(torch.sqrt(pgn2[0]), min=1e-12)
+        for s, yv, rho, a in zip(S, Y, RHO, reversed(alphas)):
+            q.addcmul_(s, a - rho * torch.dot(yv, q))
+        d = aligned(-q, pg)
+        step, accepted = 1.0, None
+        trials = 0
+        while trials < 30:
+            trials += 1
+            new, f_new, dec, gn2_new = evaluate(x, d, xi, pg, step)
+            if dec < 0 and f_new <= f + 1e-4 * dec:
+                accepted = new
+                break
+            if dec >= 0 and S:          # not a descent direction: reset memory, restart the search
+                S, Y, RHO = [], [], []
+                d = aligned(-pg / torch.clamp(torch.sqrt(pgn2[0]), min=1e-12), pg)
+                step, trials = 1.0, 0
+                continue
+            step *= 0.5
+        if accepted is None:            # no decrease along the steepest pseudo-gradient direction
+            break
+        x_new, xs_new, g_new, pg_new, xi_new, pgn2_new = accepted
+        s_vec, y_vec = x_new - x, g_new - g
+        sy = torch.dot(s_vec, y_vec)
+        if read(sy.reshape(1))[0] > 1e-12:
+            S.append(s_vec)
+            Y.append(y_vec)
+            RHO.append(1.0 / sy)
+            gamma = sy / torch.dot(y_vec, y_vec)
+            if len(S) > history_size:
+                S.pop(0)
+                Y.pop(0)
+                RHO.pop(0)
+        improvement = (f - f_new) / max(abs(f_new), abs(f), 1e-12)
+        x, xs, g, pg, xi, pgn2, f, gn2 = x_new, xs_new, g_new, pg_new, xi_new, pgn2_new, f_new, gn2_new
+        history.append(f)
+        if abs(improvement) < tol:
+            break
+    coef = xs.cpu().numpy()        # scale * x[:F]: a coefficient left at exactly 0.0 stays 0.0
+    intercept = float(x[F]) if fit_intercept else 0.0
     return coef, intercept, history

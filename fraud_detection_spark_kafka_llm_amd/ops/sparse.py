@@ -93,6 +93,68 @@ def spmv_t(indptr, idx, val, r: torch.Tensor, cols: int, threads: int = 0) -> to
     return g
 
 
+def lr_limits() -> dict:
+    """Structural constants of the logistic-regression kernels (rows per partial of ``lr_forward``,
+    width of the reducer, workgroup size and workgroup cap of the parameter passes)."""
+    return dict(native.lib().lr_limits())
+
+
+def lr_reduce(partials: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sums of the rows of ``partials`` [K, P] in the reducer's fixed order (it depends on P alone)."""
+    if out is None:
+        out = torch.empty(partials.shape[0], dtype=torch.float64, device=partials.device)
+    native.lib().lr_reduce(partials, out)
+    return out
+
+
+def lr_forward(indptr, idx, val, xs: torch.Tensor, b: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
+               want_rows: bool = False, out: Optional[torch.Tensor] = None, threads: int = 0):
+    """Fused evaluation of binary logistic regression over a CSR: margins ``X xs + b`` (bitwise
+    ``spmv(...) + b``), residuals ``r = w (sigma(m) - y)`` and the sums ``(sum w loss, sum r)``, written
+    to ``out`` [2] when given. Returns ``(r, sums)``, or ``(r, sums, loss_row, margin)`` with
+    ``want_rows``. ``b`` is a one-element tensor on the CSR's device."""
+    dev = indptr.device
+    n = indptr.numel() - 1
+    C = native.lib()
+    per = int(C.lr_limits()["rows_per_partial"])
+    partials = torch.empty((2, (n + per - 1) // per), dtype=torch.float64, device=dev)
+    r = torch.empty(n, dtype=torch.float64, device=dev)
+    loss_row = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    margin = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    C.lr_forward(indptr, idx, val, xs, b, y, w, r, loss_row, margin, partials, threads)
+    sums = lr_reduce(partials, out)
+    return (r, sums, loss_row, margin) if want_rows else (r, sums)
+
+
+def lr_owlqn_step(x: torch.Tensor, d: torch.Tensor, xi: torch.Tensor, pg: torch.Tensor, scale: torch.Tensor,
+                  t: float, threads: int = 0):
+    """OWL-QN trial point over ``F + 1`` parameters (the last is the intercept, never projected):
+    ``x_new = pi(x + t d; xi)`` with coefficients that leave their orthant set to exactly 0.0 and
+    ``xs_new = scale * x_new[:F]``. Returns ``(x_new, xs_new, sums)`` with
+    ``sums = (|x_new[:F]|_1, x_new[:F] . x_new[:F], pg . (x_new - x))``."""
+    C = native.lib()
+    n = x.numel()
+    x_new = torch.empty_like(x)
+    xs_new = torch.empty(n - 1, dtype=torch.float64, device=x.device)
+    partials = torch.empty((3, int(C.lr_param_groups(n))), dtype=torch.float64, device=x.device)
+    C.lr_owlqn_step(x, d, xi, pg, scale, float(t), x_new, xs_new, partials, threads)
+    return x_new, xs_new, lr_reduce(partials)
+
+
+def lr_pseudo_grad(parts: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, wsum: float, l1: float, l2: float,
+                   fit_intercept: bool = True, threads: int = 0):
+    """Gradient pass over ``F + 1`` parameters from ``parts = (sum w loss, sum r, X^T r)`` [F + 2]:
+    the smooth gradient ``g = scale X^T r / W + l2 beta`` (intercept: ``sum r / W``), the
+    pseudo-gradient ``pg`` of ``l1 |beta|_1`` and the orthant ``xi``. Returns ``(g, pg, xi, |pg|^2)``."""
+    C = native.lib()
+    n = x.numel()
+    g, pg, xi = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    partials = torch.empty((1, int(C.lr_param_groups(n))), dtype=torch.float64, device=x.device)
+    C.lr_pseudo_grad(parts, scale, x, float(wsum), float(l1), float(l2), bool(fit_intercept), g, pg, xi, partials,
+                     threads)
+    return g, pg, xi, lr_reduce(partials)
+
+
 def term_presence_by_label(vc, term_ids, labels, num_classes: int = 2) -> torch.Tensor:
     """K-19: documents containing each of ``term_ids`` per label, in one pass over the CSR
     (replaces the reference's one Spark job per word, fraud_detection_spark.py:256-269).
