@@ -238,6 +238,24 @@ def build_lr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     return out
 
 
+def build_sim_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/sim_selftest.cpp`` + the top-k cosine retrieval host twins (``sim_cpu.cpp``) as a
+    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
+    ``build_lr_selftest`` (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("sim_selftest_asan" if sanitize else "sim_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "sim_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "sim_cpu.cpp"}"\n#include "{CSRC / "tests" / "sim_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -252,7 +270,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the n-gram mode of the featurizer's host twin")
     ap.add_argument("--lr-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the elastic-net logistic-regression host twins")
+    ap.add_argument("--sim-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the top-k cosine retrieval host twins")
     args = ap.parse_args(argv)
+    if args.sim_selftest:
+        return subprocess.run([str(build_sim_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.lr_selftest:
         return subprocess.run([str(build_lr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.ngram_selftest:

@@ -155,6 +155,100 @@ def lr_pseudo_grad(parts: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, ws
     return g, pg, xi, lr_reduce(partials)
 
 
+def sim_limits() -> dict:
+    """Structural constants of the retrieval kernels: largest ``k``, distinct terms of a query held
+    in LDS, corpus rows per workgroup chunk, queries per pass over a chunk, wave and workgroup size."""
+    return dict(native.lib().sim_limits())
+
+
+@dataclass
+class SimIndex:
+    """A CSR corpus prepared for ``topk_cosine``: ``norms[r] = sqrt(sum val^2)`` in spmv's order."""
+    indptr: torch.Tensor
+    idx: torch.Tensor
+    val: torch.Tensor
+    norms: torch.Tensor
+    size: int
+
+    @property
+    def rows(self) -> int:
+        return int(self.indptr.numel() - 1)
+
+
+def sim_norms(indptr: torch.Tensor, val: torch.Tensor, threads: int = 0) -> torch.Tensor:
+    norms = torch.empty(indptr.numel() - 1, dtype=torch.float64, device=indptr.device)
+    native.lib().sim_norms(indptr, val, norms, threads)
+    return norms
+
+
+def sim_index(vc, threads: int = 0) -> SimIndex:
+    """Index of a ``VectorColumn`` whose rows hold ascending, distinct feature ids (what the
+    featurizer writes)."""
+    indptr, idx, val = _csr(vc)
+    if indptr.numel() < 1 or int(indptr[0]) != 0 or int(indptr[-1]) != idx.numel():
+        raise ValueError("indptr does not span the CSR's entries")
+    return SimIndex(indptr, idx, val, sim_norms(indptr, val, threads), int(vc.size))
+
+
+def topk_cosine(index: SimIndex, queries_vc, k: int, threads: int = 0, chunk_rows: int = 0,
+                queries_per_pass: int = 0):
+    """Exact top-``k`` cosine neighbours of every row of ``queries_vc`` among the index's rows:
+    ``(rows int64 [Q, min(k, N)], sims float64 [Q, min(k, N)])`` by descending similarity, ties by
+    ascending row. ``dot(r, q)`` is ``spmv(corpus, dense(q))[r]`` bit for bit and
+    ``sim = dot / max(norm[r] * |q|, 1e-12)``, so the result is a pure function of (corpus, queries,
+    k): ``chunk_rows`` and ``queries_per_pass`` (0 = default) only change how the work is split. A
+    query with more than ``query_cap`` distinct terms takes the dense-query path (``spmv``, the same
+    division, a stable descending argsort): the same contract and the same bits."""
+    lim = sim_limits()
+    k = int(k)
+    if not 1 <= k <= lim["k_max"]:
+        raise ValueError(f"k must lie in 1 .. {lim['k_max']}")
+    if queries_vc.size != index.size:
+        raise ValueError("queries and corpus live in different feature spaces")
+    q_indptr, q_idx, q_val = _csr(queries_vc)
+    dev = index.indptr.device
+    if q_indptr.device != dev:
+        raise ValueError("queries and corpus live on different devices")
+    q_val = q_val.to(torch.float64)
+    Q, N = int(q_indptr.numel() - 1), index.rows
+    kk = min(k, N)
+    rows = torch.empty((Q, kk), dtype=torch.int64, device=dev)
+    sims = torch.empty((Q, kk), dtype=torch.float64, device=dev)
+    if Q == 0 or N == 0:
+        return rows, sims
+    C = native.lib()
+    qp = q_indptr.cpu()
+    long_q = torch.nonzero(qp[1:] - qp[:-1] > lim["query_cap"]).flatten().tolist()
+    if not long_q:
+        C.sim_topk(index.indptr, index.idx, index.val, index.norms, q_indptr, q_idx, q_val, k, rows, sims,
+                   chunk_rows, queries_per_pass, threads)
+        return rows, sims
+    is_long = set(long_q)
+    short = [q for q in range(Q) if q not in is_long]
+    if short:
+        sel = torch.tensor(short, dtype=torch.int64)
+        lens = (qp[1:] - qp[:-1])[sel]
+        sp = torch.zeros(len(short) + 1, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=sp[1:])
+        take = torch.cat([torch.arange(int(qp[q]), int(qp[q + 1])) for q in short]).to(dev)
+        r_s = torch.empty((len(short), kk), dtype=torch.int64, device=dev)
+        s_s = torch.empty((len(short), kk), dtype=torch.float64, device=dev)
+        C.sim_topk(index.indptr, index.idx, index.val, index.norms, sp.to(dev), q_idx[take].contiguous(),
+                   q_val[take].contiguous(), k, r_s, s_s, chunk_rows, queries_per_pass, threads)
+        rows[sel.to(dev)] = r_s
+        sims[sel.to(dev)] = s_s
+    q_norms = sim_norms(q_indptr, q_val, threads)
+    for q in long_q:
+        a, b = int(qp[q]), int(qp[q + 1])
+        x = torch.zeros(index.size, dtype=torch.float64, device=dev)
+        x[q_idx[a:b].to(torch.int64)] = q_val[a:b]
+        dot = spmv(index.indptr, index.idx, index.val, x, threads)
+        s = dot / torch.clamp(index.norms * q_norms[q], min=1e-12)
+        top = torch.argsort(s, descending=True, stable=True)[:kk]
+        rows[q], sims[q] = top, s[top]
+    return rows, sims
+
+
 def term_presence_by_label(vc, term_ids, labels, num_classes: int = 2) -> torch.Tensor:
     """K-19: documents containing each of ``term_ids`` per label, in one pass over the CSR
     (replaces the reference's one Spark job per word, fraud_detection_spark.py:256-269).

@@ -3,7 +3,8 @@
 Same public surface as the reference's ``DeepSeekClassificationAgent``
 (/root/reference/utils/agent_api.py:124-208): ``model``, ``analyzer``, ``historical_data``,
 ``preprocess_text``, ``predict_and_get_label``, ``classify_and_explain``,
-``find_similar_historical_cases``. Differences:
+``find_similar_historical_cases`` (and its batched form,
+``find_similar_historical_cases_batch``). Differences:
 
 * one fused kernel launch per call (the reference runs two Spark jobs per prediction);
 * ``predict_batch`` scores a whole list in one launch (batch CSV tab, streaming);
@@ -40,6 +41,7 @@ class ClassificationAgent:
         self.analyzer = analyzer or Analyzer(llm if llm is not None else make_llm())
         self._historical: Optional[Frame] = None
         self._hist_index = None
+        self._sim_index = None
         if historical_data_path:
             self.historical_data = Frame.read_csv(historical_data_path)
 
@@ -54,6 +56,7 @@ class ClassificationAgent:
             frame = Frame.from_pandas(frame)
         self._historical = frame
         self._hist_index = None
+        self._sim_index = None
 
     # ------------------------------------------------------------------ inference
     def preprocess_text(self, text: str) -> Frame:
@@ -99,6 +102,25 @@ class ClassificationAgent:
         sims = score_csr(vc, LinearScorer(w, 0.0))[:, 0] / torch.clamp(norms * qn, min=1e-12)
         top = torch.argsort(sims, descending=True, stable=True)[:n].cpu().numpy()
         return hd.take_rows(top).collect()
+
+    def find_similar_historical_cases_batch(self, dialogues: Sequence[str], n: int = 3, with_scores: bool = False):
+        """``find_similar_historical_cases`` for a list of dialogues in one featurize launch and one
+        exact top-k retrieval (``serve.similar.HistoricalIndex``): one list of historical rows per
+        dialogue, best first, ties by historical row number; with ``with_scores`` a
+        ``(cases, rows, sims)`` triple with the row numbers and cosine similarities as arrays
+        ``[len(dialogues), min(n, N)]``. ``None`` under the single-query method's conditions."""
+        hd = self._historical
+        if hd is None or hd.count() == 0 or "dialogue" not in hd:
+            return None
+        if self._sim_index is None:
+            from .similar import HistoricalIndex
+
+            self._sim_index = HistoricalIndex(self.fused, hd)
+        rows, sims = self._sim_index.query(list(dialogues), n)
+        flat = hd.take_rows(rows.reshape(-1)).collect()
+        k = rows.shape[1]
+        cases = [flat[i * k:(i + 1) * k] for i in range(rows.shape[0])]
+        return (cases, rows, sims) if with_scores else cases
 
     def _features(self, texts):
         fp = self.fused
@@ -151,8 +173,19 @@ class ClassificationAgent:
                 "        Words of this dialogue with their signed contribution to the classifier's fraud score "
                 f"(positive pushes towards fraud, negative away from it), strongest first: {listed}")
 
+    def insight_from_cases(self, dialogue: str, cases, temperature: float = 0.7) -> str:
+        """The LLM's comparison of ``dialogue`` with the historical rows ``cases``."""
+        cases_str = "\n".join(str(dict(r)) for r in cases)
+        return self.analyzer.llm.generate(
+            "Compare this new case with historical patterns:\n"
+            f"New Case: {dialogue}\n\n"
+            f"Historical Similar Cases:\n{cases_str}\n\n"
+            "Identify any consistent patterns or anomalies.", temperature)
+
     def classify_and_explain(self, dialogue: str, temperature: float = 0.7, prediction: Optional[dict] = None,
-                             with_history: bool = True, evidence: int = 0) -> dict:
+                             with_history: bool = True, evidence: int = 0, cases=None) -> dict:
+        """``cases``: historical rows already looked up for this dialogue (e.g. one element of
+        ``find_similar_historical_cases_batch``); when given, no lookup is made."""
         res = prediction or self.predict_and_get_label(dialogue)
         words = self.contributing_words(dialogue, evidence) if evidence > 0 else None
         if words is None:
@@ -161,15 +194,11 @@ class ClassificationAgent:
             prompt = self.analyzer.create_prompt(dialogue, res["prediction"], res["confidence"])
             analysis = self.analyzer.llm.generate(prompt + self.evidence_paragraph(words), temperature)
         insight = None
-        if with_history and self._historical is not None:
-            cases = self.find_similar_historical_cases(dialogue)
+        if cases is not None or (with_history and self._historical is not None):
+            if cases is None:
+                cases = self.find_similar_historical_cases(dialogue)
             if cases:
-                cases_str = "\n".join(str(dict(r)) for r in cases)
-                insight = self.analyzer.llm.generate(
-                    "Compare this new case with historical patterns:\n"
-                    f"New Case: {dialogue}\n\n"
-                    f"Historical Similar Cases:\n{cases_str}\n\n"
-                    "Identify any consistent patterns or anomalies.", temperature)
+                insight = self.insight_from_cases(dialogue, cases, temperature)
         out = {"prediction": res["prediction"], "confidence": res["confidence"], "analysis": analysis,
                "historical_insight": insight}
         if words is not None:

@@ -37,8 +37,10 @@ def analyze_single(agent, text: str, temperature: float = 0.7, with_history: boo
     return out
 
 
-def predict_dataframe(agent, df):
-    """Batch tab: one fused launch for the whole uploaded CSV -> result table + CSV text."""
+def predict_dataframe(agent, df, similar: int = 0):
+    """Batch tab: one fused launch for the whole uploaded CSV -> result table + CSV text. With
+    ``similar > 0`` and historical data loaded, one batched lookup adds a ``similar_cases`` column:
+    the row numbers of the ``similar`` closest historical dialogues, best first, joined by ``;``."""
     import pandas as pd
 
     if "dialogue" not in df.columns:
@@ -48,6 +50,10 @@ def predict_dataframe(agent, df):
     out = pd.DataFrame({"dialogue": texts,
                         "predicted_label": [LABEL_MAPPING.get(int(r["prediction"]), r["prediction"]) for r in res],
                         "confidence": [format_confidence(r["confidence"]) for r in res]})
+    if similar > 0 and texts:
+        found = agent.find_similar_historical_cases_batch(texts, n=similar, with_scores=True)
+        if found is not None:
+            out["similar_cases"] = [";".join(str(int(r)) for r in rows) for rows in found[1]]
     return out, out.to_csv(index=False)
 
 
@@ -64,8 +70,11 @@ class KafkaMonitor:
     """One iteration = consume a small batch, classify it in one launch, produce, commit."""
 
     def __init__(self, agent, consumer, producer, output_topic: Optional[str], explain: bool = True,
-                 temperature: float = 0.7, batch: int = 64):
+                 temperature: float = 0.7, batch: int = 64, history: int = 0):
+        """``history > 0``: one batched lookup of the ``history`` closest historical cases per
+        ``step`` feeds the explanations, so ``historical_insight`` is filled (needs ``explain``)."""
         self.agent, self.consumer, self.producer = agent, consumer, producer
+        self.history = history
         self.topic, self.explain, self.temperature, self.batch = output_topic, explain, temperature, batch
         self.messages: list = []
         self.errors: list = []
@@ -85,10 +94,16 @@ class KafkaMonitor:
         if not good:
             return 0
         preds = self.agent.predict_batch(texts)
-        for m, t, p in zip(good, texts, preds):
+        found = None
+        if self.explain and self.history > 0:
+            found = self.agent.find_similar_historical_cases_batch(texts, n=self.history)
+        for i, (m, t, p) in enumerate(zip(good, texts, preds)):
             rec = {"prediction": p["prediction"], "confidence": p["confidence"], "analysis": None,
                    "historical_insight": None}
-            if self.explain:
+            if self.explain and found is not None:
+                r = self.agent.classify_and_explain(t, temperature=self.temperature, prediction=p, cases=found[i])
+                rec["analysis"], rec["historical_insight"] = r["analysis"], r["historical_insight"]
+            elif self.explain:
                 r = self.agent.classify_and_explain(t, temperature=self.temperature, prediction=p, with_history=False)
                 rec["analysis"] = r["analysis"]
             self.messages.append({"id": m.key(), "dialogue": t, **p})

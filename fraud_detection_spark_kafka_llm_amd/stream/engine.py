@@ -26,6 +26,10 @@ a log-binned histogram (``p50_ms`` / ``p95_ms`` / ``p99_ms``). LLM explanations:
 (analysis null), ``"sync"`` (inline, reference behaviour) or ``"async"`` (classification produced
 immediately; every ``explain_every``-th message is explained on a bounded thread pool and the
 explanation follows as a second record with the same key and ``"type": "explanation"``).
+``similar_cases=n`` (with an agent that holds historical data) looks the ``n`` most similar
+historical cases of a micro-batch's explained records up in one batched call
+(``agent.find_similar_historical_cases_batch``): sync records then carry a ``historical_insight``
+from those cases, async explanation records gain the key.
 """
 from __future__ import annotations
 
@@ -434,7 +438,7 @@ class StreamingEngine:
                  batch_max: int = 4096, max_latency_ms: float = 5.0, explain: str = "none", agent=None,
                  slots: int = 0, max_bytes: int = 64 << 20, field_name: str = "text", commit: bool = True,
                  explain_every: int = 1, explain_max_pending: int = 1024, poll_ms: float = 20.0,
-                 ring: Optional[PinnedRing] = None):
+                 ring: Optional[PinnedRing] = None, similar_cases: int = 0):
         if explain != "none" and agent is None:
             raise ValueError("explain requires an agent (LLM analyzer)")
         if output_topic is None:
@@ -449,6 +453,10 @@ class StreamingEngine:
         self.poll_s = poll_ms / 1000.0
         self.explain, self.agent = explain, agent
         self.explain_every, self.explain_max_pending = max(1, explain_every), explain_max_pending
+        # > 0: explanations carry a historical insight from this many similar historical cases, looked
+        # up once per micro-batch (agent.find_similar_historical_cases_batch); 0: no batched lookup
+        self.similar_cases = max(0, int(similar_cases))
+        self._batch_cases: Optional[dict] = None
         self.field = field_name
         self.commit = commit
         nslots = max(slots, scorer.depth + len(self.consumers) + 2)
@@ -622,10 +630,16 @@ class StreamingEngine:
         offs = slot.offsets.numpy()
         if self.explain == "sync":
             enc = None
+            if self._similar_on():      # one lookup for the micro-batch, ahead of the produce loop
+                ok = [i for i in range(n) if status[i] == 0]
+                texts = [bytes(data[offs[i]:offs[i + 1]]).decode("utf-8", "replace") for i in ok]
+                found = self.agent.find_similar_historical_cases_batch(texts, n=self.similar_cases) if ok else None
+                self._batch_cases = dict(zip(ok, found)) if found is not None else None
         else:
             enc = self._encode(status, pred, p1, slot)
         for seg, entry in zip(b.segments, b.entries):
             self._produce_segment(seg, entry, status, pred, p1, data, offs, enc)
+        self._batch_cases = None
         if self.explain == "async":
             self._submit_explanations(b, status, pred, p1, data, offs)
         self._seen += n
@@ -685,8 +699,12 @@ class StreamingEngine:
                     continue
                 text = bytes(data[offs[i]:offs[i + 1]]).decode("utf-8", "replace")
                 if enc is None:
-                    r = self.agent.classify_and_explain(text, prediction={"prediction": float(pred[i]),
-                                                                          "confidence": float(p1[i])})
+                    p = {"prediction": float(pred[i]), "confidence": float(p1[i])}
+                    if self._batch_cases is not None:       # looked up once for the micro-batch
+                        r = self.agent.classify_and_explain(text, prediction=p, with_history=True,
+                                                            cases=self._batch_cases[i])
+                    else:
+                        r = self.agent.classify_and_explain(text, prediction=p)
                     vl.append(self._record_py(pred[i], p1[i], text, r["analysis"], r["historical_insight"]))
                 elif enc[2][i] == 0:
                     vl.append(bytes(enc[0][enc[1][i]:enc[1][i + 1]]))
@@ -745,8 +763,15 @@ class StreamingEngine:
                 log.warning("commit failed: %s", e)
 
     # ------------------------------------------------------------------ explanations
+    def _similar_on(self) -> bool:
+        return (self.similar_cases > 0 and hasattr(self.agent, "find_similar_historical_cases_batch")
+                and getattr(self.agent, "historical_data", None) is not None)
+
     def _submit_explanations(self, b: _Batch, status, pred, p1, data, offs) -> None:
+        """The sampled records of the micro-batch go to the pool; with ``similar_cases`` their similar
+        historical cases are looked up first, in one call for all of them."""
         every = self.explain_every
+        picked = []
         for seg in b.segments:
             first = (-(self._seen + seg.a)) % every
             for i in range(seg.a + first, seg.b, every):
@@ -758,16 +783,31 @@ class StreamingEngine:
                         continue
                     self._explain_pending += 1
                 text = bytes(data[offs[i]:offs[i + 1]]).decode("utf-8", "replace")
-                self._pool.submit(self._explain_async, seg.key(i - seg.a), text, float(pred[i]), float(p1[i]))
+                picked.append((seg.key(i - seg.a), text, float(pred[i]), float(p1[i])))
+        cases = [None] * len(picked)
+        if picked and self._similar_on():
+            try:
+                cases = self.agent.find_similar_historical_cases_batch([t for _, t, _, _ in picked],
+                                                                       n=self.similar_cases) or cases
+            except Exception as e:   # the explanations still go out, with a null insight
+                log.error("similar-case lookup failed: %s", e)
+                cases = [[]] * len(picked)
+        for args, c in zip(picked, cases):
+            self._pool.submit(self._explain_async, *args, c)
 
-    def _explain_async(self, key, text, pred, conf) -> None:
+    def _explain_async(self, key, text, pred, conf, cases=None) -> None:
         try:
             analysis = self.agent.analyzer.analyze_prediction(text, pred, conf)
         except Exception as e:   # the classification was already produced
             analysis = f"explanation failed: {e}"
+        rec = {"type": "explanation", "prediction": pred, "confidence": conf, "analysis": analysis}
+        if cases is not None:    # similar_cases > 0: the record carries the key, null without cases
+            try:
+                rec["historical_insight"] = self.agent.insight_from_cases(text, cases) if cases else None
+            except Exception as e:
+                rec["historical_insight"] = f"historical insight failed: {e}"
         try:
-            self.producer.produce(self.topic, key=key, value=json.dumps({"type": "explanation", "prediction": pred,
-                                                                          "confidence": conf, "analysis": analysis}))
+            self.producer.produce(self.topic, key=key, value=json.dumps(rec))
         finally:
             with self._lock:
                 self._explain_pending -= 1

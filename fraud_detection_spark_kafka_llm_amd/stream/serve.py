@@ -79,6 +79,10 @@ def main(argv=None) -> int:
                     help="one consumer (and reader thread) per input partition instead of one subscriber")
     ap.add_argument("--group-clients", type=int, default=0,
                     help="run the Kafka clients as this many consumer-group processes around this GPU process")
+    ap.add_argument("--similar-cases", type=int, default=0,
+                    help="explanations carry a historical insight from this many similar historical cases, looked "
+                         "up once per micro-batch (needs --explain and --historical-data)")
+    ap.add_argument("--historical-data", default=None, help="CSV of historical dialogues (column 'dialogue')")
     Config.add_cli_args(ap)
     args = ap.parse_args(argv)
     load_dotenv()
@@ -104,7 +108,7 @@ def main(argv=None) -> int:
     else:
         devices = [torch.device("cpu")]
     llm = make_llm() if args.explain != "none" else StubLLM()   # no LLM calls without --explain
-    agent = ClassificationAgent(args.model, llm=llm, device=devices[0])
+    agent = ClassificationAgent(args.model, historical_data_path=args.historical_data, llm=llm, device=devices[0])
     if args.group_clients > 0:
         return _serve_group(args, agent, devices, out_topic=os.getenv("KAFKA_OUTPUT_TOPIC", DEFAULT_OUTPUT))
     consumer = get_partition_consumers() if args.partition_readers else get_kafka_consumer()
@@ -113,7 +117,8 @@ def main(argv=None) -> int:
     if args.metrics_port:
         start_metrics_server(args.metrics_port)
     eng = StreamingEngine.from_agent(agent, consumer, producer, out_topic, devices=devices, batch_max=args.batch,
-                                     max_latency_ms=args.max_latency_ms, explain=args.explain)
+                                     max_latency_ms=args.max_latency_ms, explain=args.explain,
+                                     similar_cases=args.similar_cases)
     log.info("serving %s on %s -> %s", args.model, [str(d) for d in devices], out_topic)
     try:
         stats = eng.run(max_messages=args.max_messages, idle_timeout_s=args.idle_timeout)
