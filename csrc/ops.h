@@ -83,6 +83,16 @@ void lr_owlqn_step_cpu(const LrStepArgs& a, int threads);
 void launch_lr_pseudo_grad(const LrGradArgs& a, hipStream_t stream);
 void lr_pseudo_grad_cpu(const LrGradArgs& a, int threads);
 
+// ---------------------------------------------------------------- Naive Bayes (nb_kernels.hip / nb_cpu.cpp)
+template <class V> struct NbSumArgs;   // nb.h
+template <class V> struct NbScoreArgs;
+// exact int64 class-conditional sums (any grid, chunk, hot set or thread count gives the same bits)
+template <class V> void launch_nb_sums(const NbSumArgs<V>& a, hipStream_t stream);
+template <class V> void nb_sums_cpu(const NbSumArgs<V>& a, int threads);
+// raw[r, c] = b_c + X W[:, c] in spmv's order
+template <class V> void launch_nb_score(const NbScoreArgs<V>& a, hipStream_t stream);
+template <class V> void nb_score_cpu(const NbScoreArgs<V>& a, int threads);
+
 // ---------------------------------------------------------------- feature-major order (sort_kernels.hip)
 template <class V>
 struct FeatureOrderArgs {

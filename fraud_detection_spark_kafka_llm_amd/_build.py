@@ -256,6 +256,24 @@ def build_sim_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     return out
 
 
+def build_nb_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/nb_selftest.cpp`` + the Naive Bayes host twins (``nb_cpu.cpp``) as a standalone
+    executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_sim_selftest``
+    (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("nb_selftest_asan" if sanitize else "nb_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "nb_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "nb_cpu.cpp"}"\n#include "{CSRC / "tests" / "nb_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -272,7 +290,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the elastic-net logistic-regression host twins")
     ap.add_argument("--sim-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the top-k cosine retrieval host twins")
+    ap.add_argument("--nb-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the Naive Bayes host twins")
     args = ap.parse_args(argv)
+    if args.nb_selftest:
+        return subprocess.run([str(build_nb_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.sim_selftest:
         return subprocess.run([str(build_sim_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.lr_selftest:

@@ -1,4 +1,4 @@
-"""Classifiers: LogisticRegression, DecisionTreeClassifier, RandomForestClassifier (+ models).
+"""Classifiers: LogisticRegression, DecisionTreeClassifier, RandomForestClassifier, NaiveBayes (+ models).
 
 Models score through the native engine: either fused with the text featurizer
 (``ml.fused``; one gfx950 launch from raw bytes to scores) or over an existing feature column
@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from ..io import spark_format as sf
-from ..ops.text import LinearScorer, TreeArrays
+from ..ops.text import ClassLinearScorer, LinearScorer, TreeArrays
 from .base import Estimator, Model, Param, register
 from .frame import Frame
 from .linalg import DenseVector, VectorColumn
@@ -119,6 +119,20 @@ def _normalize(raw: torch.Tensor) -> torch.Tensor:
     return torch.where(s != 0, raw / torch.where(s != 0, s, torch.ones_like(s)), raw)
 
 
+def _linear_contributions(vc: VectorColumn, weights: torch.Tensor, bias: float, nf: int) -> VectorColumn:
+    """Linear models: every row stores its own entries ``w_f * x_f``, then ``bias`` at index ``nf``."""
+    indptr, idx, val = vc.csr()
+    dev, n = indptr.device, indptr.numel() - 1
+    rows = torch.arange(n + 1, dtype=torch.int64, device=dev)
+    row_of = torch.repeat_interleave(rows[:-1], indptr[1:] - indptr[:-1], output_size=int(idx.numel()))
+    out_idx = torch.full((int(idx.numel()) + n,), nf, dtype=torch.int32, device=dev)
+    out_val = torch.full((int(idx.numel()) + n,), bias, dtype=torch.float64, device=dev)
+    pos = torch.arange(int(idx.numel()), dtype=torch.int64, device=dev) + row_of
+    out_idx[pos] = idx.to(torch.int32)
+    out_val[pos] = weights[idx.to(torch.int64)] * val.to(torch.float64)
+    return VectorColumn(nf + 1, indptr + rows, out_idx, out_val)
+
+
 # ============================================================================ logistic regression
 class _LRParams(_PredictorParams):
     _params = [Param("family", "binomial|multinomial|auto", "auto", str),
@@ -198,16 +212,7 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
         vc = self._features_column(features)
         if vc.size != self.numFeatures:
             raise ValueError(f"features have size {vc.size}, model expects {self.numFeatures}")
-        indptr, idx, val = vc.csr()
-        dev, n, nf = indptr.device, indptr.numel() - 1, self.numFeatures
-        rows = torch.arange(n + 1, dtype=torch.int64, device=dev)
-        row_of = torch.repeat_interleave(rows[:-1], indptr[1:] - indptr[:-1], output_size=int(idx.numel()))
-        out_idx = torch.full((int(idx.numel()) + n,), nf, dtype=torch.int32, device=dev)
-        out_val = torch.full((int(idx.numel()) + n,), self.intercept, dtype=torch.float64, device=dev)
-        pos = torch.arange(int(idx.numel()), dtype=torch.int64, device=dev) + row_of
-        out_idx[pos] = idx.to(torch.int32)
-        out_val[pos] = self.scorer().weights(dev)[idx.to(torch.int64)] * val.to(torch.float64)
-        return VectorColumn(nf + 1, indptr + rows, out_idx, out_val)
+        return _linear_contributions(vc, self.scorer().weights(vc.device), self.intercept, self.numFeatures)
 
     def postprocess_numpy(self, raw: np.ndarray):
         p = np.exp(-raw[:, 0])
@@ -437,3 +442,159 @@ class RandomForestClassificationModel(_RFParams, TreeClassificationModelBase):
             self._tree_weights = np.ones(len(self._trees))
         self._num_features = int(md.get("numFeatures", 0))
         self._arrays = None
+
+
+# ============================================================================ naive Bayes
+class _NBParams(_PredictorParams):
+    _params = [Param("smoothing", "additive (Laplace / Lidstone) smoothing", 1.0, float),
+               Param("modelType", "multinomial|bernoulli (complement and gaussian are not supported)",
+                     "multinomial", str),
+               Param("weightCol", "weight column", None, str, has_default=False),
+               Param("thresholds", "per-class thresholds: the prediction is the first argmax of p_c / t_c",
+                     None, list, has_default=False)]
+
+
+@register("org.apache.spark.ml.classification.NaiveBayes")
+class NaiveBayes(_NBParams, Estimator):
+    """Spark's ``NaiveBayes`` (multinomial and Bernoulli) with an exact fixed-point fit
+    (``models/nb.py``): host fits, device fits and every world size give the same model bits. Data
+    parallelism is through the ambient process group, as for ``LogisticRegression``."""
+    _uid_prefix = "NaiveBayes"
+
+    def _fit(self, frame: Frame) -> "NaiveBayesModel":
+        from ..models.nb import fit_naive_bayes
+
+        w = frame.column(self.getWeightCol()) if self.isSet("weightCol") else None
+        res = fit_naive_bayes(frame.column(self.getFeaturesCol()), frame.column(self.getLabelCol()), weights=w,
+                              smoothing=self.getSmoothing(), model_type=self.getModelType())
+        m = NaiveBayesModel(res["pi"], res["theta"], uid=self.uid)
+        m._paramMap.update(self._paramMap)
+        return m
+
+
+@register("org.apache.spark.ml.classification.NaiveBayesModel")
+class NaiveBayesModel(_NBParams, ClassificationModelBase):
+    """``pi`` [C] class log-priors and ``theta`` [C, F] feature log-probabilities. ``rawPrediction`` is
+    the ``C`` class scores of ``ops.sparse.score_csr`` (``nb_score``), ``probability`` Spark's
+    ``raw2probability`` (subtract the row maximum, ``exp``, divide by the sum).
+
+    A binary model also serves through the single-launch paths: ``scorer()`` is the margin
+    ``raw_1 - raw_0`` as one ``LinearScorer``, and ``postprocess`` of a margin ``m`` [N, 1] gives
+    ``probability = [sigma(-m), sigma(m)]`` and ``rawPrediction = [0, m]``: Spark's ``rawPrediction``
+    minus the per-row constant ``raw_0`` (probabilities and predictions are those of the class
+    scores up to rounding). Only the serving paths (``FusedPipeline.predict``, the agent, the
+    streaming engine) see that form; ``transform`` gives Spark's ``rawPrediction``."""
+    _uid_prefix = "NaiveBayes"
+
+    def __init__(self, pi=None, theta=None, **kw):
+        super().__init__(**kw)
+        self._set_model(pi if pi is not None else np.zeros(0), theta if theta is not None else np.zeros((0, 0)))
+
+    def _set_model(self, pi, theta) -> None:
+        self.pi = np.asarray(pi, dtype=np.float64).reshape(-1)
+        self.theta = np.asarray(theta, dtype=np.float64).reshape(self.pi.size, -1)
+        self.sigma = np.zeros((0, 0))
+        self._class_scorer = self._scorer = None
+
+    @property
+    def numClasses(self) -> int:  # noqa: N802
+        return int(self.pi.size)
+
+    @property
+    def numFeatures(self) -> int:  # noqa: N802
+        return int(self.theta.shape[1])
+
+    def class_scorer(self) -> ClassLinearScorer:
+        if self._class_scorer is None:
+            from ..models.nb import class_linear
+
+            self._class_scorer = ClassLinearScorer(*class_linear(self.pi, self.theta, self.getModelType()))
+        return self._class_scorer
+
+    def scorer(self) -> LinearScorer:
+        """Binary models: the margin ``raw_1 - raw_0`` (differences taken once in fp64)."""
+        if self.numClasses != 2:
+            raise ValueError(f"the single-launch and streaming paths score binary models only; this Naive Bayes "
+                             f"model has {self.numClasses} classes (use transform / predictRaw)")
+        if self._scorer is None:
+            cs = self.class_scorer()
+            self._scorer = LinearScorer(cs.W[:, 1] - cs.W[:, 0], float(cs.b[1] - cs.b[0]))
+        return self._scorer
+
+    def _thresholds(self, like: torch.Tensor) -> Optional[torch.Tensor]:
+        if not self.isSet("thresholds"):
+            return None
+        t = torch.as_tensor(np.asarray(self.getThresholds(), dtype=np.float64)).to(like.device)
+        if t.numel() != self.numClasses or bool((t < 0).any()) or int((t == 0).sum()) > 1:
+            raise ValueError("thresholds needs one non-negative entry per class, at most one of them 0")
+        return t
+
+    def _predict_from(self, prob: torch.Tensor) -> torch.Tensor:
+        t = self._thresholds(prob)
+        if t is None:
+            return _argmax_prediction(prob)
+        zero = torch.where(prob == 0, torch.zeros_like(prob), torch.full_like(prob, float("inf")))
+        scaled = torch.where(t == 0, zero, prob / torch.where(t == 0, torch.ones_like(t), t))
+        return _argmax_prediction(scaled)
+
+    def postprocess(self, raw: torch.Tensor):
+        if raw.shape[1] == 1:                        # the serving paths' margin raw_1 - raw_0
+            if self.numClasses != 2:
+                raise ValueError("a margin describes a binary model")
+            m = raw[:, 0]
+            rp = torch.stack([torch.zeros_like(m), m], dim=1)
+            prob = 1.0 / (1.0 + torch.exp(-torch.stack([-m, m], dim=1)))
+            return rp, prob, self._predict_from(prob)
+        if raw.shape[1] != self.numClasses:
+            raise ValueError(f"expected [N, {self.numClasses}] class scores or an [N, 1] margin")
+        e = torch.exp(raw - raw.max(dim=1, keepdim=True).values)
+        prob = e / e.sum(dim=1, keepdim=True)
+        return raw, prob, self._predict_from(prob)
+
+    def postprocess_numpy(self, raw: np.ndarray):
+        """Streaming hot path: margin [N, 1] -> (prediction [N], sigma(m) [N])."""
+        if raw.shape[1] != 1 or self.isSet("thresholds"):
+            return super().postprocess_numpy(raw)
+        p = np.exp(-raw[:, 0])
+        np.add(p, 1.0, out=p)
+        np.reciprocal(p, out=p)
+        return (p > 1.0 - p).astype(np.float64), p
+
+    def _score(self, vc: VectorColumn) -> torch.Tensor:
+        from ..ops.sparse import score_csr
+
+        return score_csr(vc, self.class_scorer())
+
+    def _transform(self, frame: Frame) -> Frame:
+        return self.attach_outputs(frame, self._score(self._features_column(frame)))
+
+    def predictRaw(self, features) -> DenseVector:  # noqa: N802
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self._score(vc)[0].cpu().numpy())
+
+    def predictProbability(self, features) -> DenseVector:  # noqa: N802
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self.postprocess(self._score(vc))[1][0].cpu().numpy())
+
+    def predict(self, features) -> float:
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return float(self.postprocess(self._score(vc))[2][0])
+
+    def contributions(self, features) -> VectorColumn:
+        """Binary models: every row stores its own entries ``x_f * (W_f1 - W_f0)``, then the bias
+        ``b_1 - b_0`` at ``numFeatures``; a row sums to the margin ``raw_1 - raw_0``."""
+        vc = self._features_column(features)
+        sc = self.scorer()
+        w = sc.weights(vc.device)
+        if vc.size > w.numel():
+            w = torch.cat([w, torch.zeros(vc.size - w.numel(), dtype=torch.float64, device=w.device)])
+        return _linear_contributions(vc, w, sc.b, vc.size)
+
+    def _save_data(self, path) -> None:
+        sf.write_data_parquet(path, [sf.Field.vector("pi"), sf.Field.matrix("theta"), sf.Field.matrix("sigma")],
+                              [{"pi": sf.dense_vector(self.pi), "theta": sf.dense_matrix(self.theta),
+                                "sigma": sf.dense_matrix(self.sigma)}])
+
+    def _load_data(self, path, md) -> None:
+        row = sf.read_data_parquet(path).to_pylist()[0]
+        self._set_model(sf.decode_vector(row["pi"]), sf.decode_matrix(row["theta"]))

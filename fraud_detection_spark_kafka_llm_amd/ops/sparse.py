@@ -1,6 +1,7 @@
 """Sparse ops over ``VectorColumn`` CSR data (native: ``csrc/sparse_kernels.hip`` / ``sparse_cpu.cpp``)."""
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -9,7 +10,7 @@ import numpy as np
 import torch
 
 from . import native
-from .text import LinearScorer, TreeArrays, TreePaths
+from .text import ClassLinearScorer, LinearScorer, TreeArrays, TreePaths
 
 
 def _csr(vc):
@@ -39,6 +40,13 @@ def score_csr(vc, scorer, threads: int = 0) -> torch.Tensor:
             raise ValueError("tree references a feature beyond the feature space")
         out = torch.empty((n, scorer.K), dtype=torch.float64, device=dev)
         C.score_csr(indptr, idx, val, None, 0.0, scorer.tensors(dev), scorer.K, scorer.cmp_less, out, threads)
+        return out
+    if isinstance(scorer, ClassLinearScorer):
+        if scorer.W.shape[0] > vc.size:
+            raise ValueError("coefficient matrix longer than the feature space")
+        W, b = scorer.tensors(dev, vc.size)
+        out = torch.empty((n, scorer.num_classes), dtype=torch.float64, device=dev)
+        C.nb_score(indptr, idx, val, W, b, out, threads)
         return out
     raise TypeError(f"unknown scorer {type(scorer)}")
 
@@ -153,6 +161,102 @@ def lr_pseudo_grad(parts: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, ws
     C.lr_pseudo_grad(parts, scale, x, float(wsum), float(l1), float(l2), bool(fit_intercept), g, pg, xi, partials,
                      threads)
     return g, pg, xi, lr_reduce(partials)
+
+
+def nb_limits() -> dict:
+    """Structural constants of the Naive Bayes kernels: ``max_classes``, the default rows of a
+    workgroup (``chunk_rows``), the default and the largest LDS table of the hot features
+    (``table_bytes``, ``max_table_bytes``; a class holds ``bytes // (8 C)`` slots), the largest scale
+    exponent ``k_max``, ``sum_bits`` (``|S| < 2^sum_bits``), the rows whose document frequencies choose
+    the default hot set (``prefix_rows``), wave and workgroup size."""
+    return dict(native.lib().nb_limits())
+
+
+def nb_scale_exponent(tmax: float, n_rows: int) -> int:
+    """``k = min(k_max, sum_bits - n_rows.bit_length() - e)`` with ``max(tmax, 1.0) < 2^e`` (``frexp``);
+    raises ``ValueError`` when ``k < 0`` (the exact sums would not fit 2^sum_bits)."""
+    lim = nb_limits()
+    tmax = float(tmax)
+    if not math.isfinite(tmax) or tmax < 0:
+        raise ValueError(f"Naive Bayes needs finite, non-negative values and weights (largest term {tmax})")
+    e = math.frexp(max(tmax, 1.0))[1]
+    k = min(int(lim["k_max"]), int(lim["sum_bits"]) - int(n_rows).bit_length() - e)
+    if k < 0:
+        raise ValueError(f"terms up to {tmax:g} over {n_rows} rows do not fit the exact {lim['sum_bits']}-bit sums")
+    return k
+
+
+def nb_hot_set(indptr, idx, val, size: int, num_classes: int, table_bytes: int = 0) -> torch.Tensor:
+    """Default hot set of ``nb_sums``: the ``table_bytes // (8 C)`` most frequent features of the
+    first ``prefix_rows`` rows (features that occur there at all), as int32 feature ids."""
+    lim = nb_limits()
+    slots = int(table_bytes or lim["table_bytes"]) // (8 * int(num_classes))
+    rows = min(int(indptr.numel()) - 1, int(lim["prefix_rows"]))
+    if slots <= 0 or rows <= 0:
+        return torch.zeros(0, dtype=torch.int32, device=idx.device)
+    end = int(indptr[rows])
+    df = doc_freq(idx[:end], val[:end], size)
+    top = torch.topk(df, min(slots, size))
+    return top.indices[top.values > 0].to(torch.int32)
+
+
+def nb_hot_tables(hot_feat: torch.Tensor, size: int, num_classes: int) -> tuple:
+    """``(slot_of int16 [F], hot_feat int32 [H])`` of a hot set for the device pass (``slot_of`` is read
+    as uint16: -1 = 0xFFFF = not hot), or ``(None, None)`` for an empty one."""
+    if hot_feat.numel() * 8 * int(num_classes) > nb_limits()["max_table_bytes"]:
+        raise ValueError("the hot set exceeds the LDS table")
+    if hot_feat.numel() == 0:
+        return None, None
+    if int(hot_feat.min()) < 0 or int(hot_feat.max()) >= size:
+        raise ValueError("hot feature outside the feature space")
+    slot_of = torch.full((size,), -1, dtype=torch.int16, device=hot_feat.device)
+    slot_of[hot_feat.to(torch.int64)] = torch.arange(hot_feat.numel(), dtype=torch.int16, device=hot_feat.device)
+    return slot_of, hot_feat.to(torch.int32).contiguous()
+
+
+def nb_sums(vc, labels, weights, num_classes: int, k: int, kw: int, bernoulli: bool = False, hot=None,
+            threads: int = 0, chunk_rows: int = 0):
+    """Exact class-conditional sums of a CSR column for Naive Bayes, ``(S [C, F], Wq [C], cnt [C])``
+    int64: ``S[c, f] = sum rint(w_i x_ij 2^k)`` over the stored entries ``f`` of the rows of class
+    ``c``, ``Wq[c] = sum rint(w_i 2^kw)``, ``cnt[c]`` the rows of class ``c``. Integer sums do not depend
+    on order: ``hot`` (device: feature ids accumulated in LDS; ``None`` = ``nb_hot_set``, empty =
+    every entry goes to a global atomic), ``chunk_rows`` and ``threads`` change the speed only.
+    Raises ``ValueError`` for a label that is no integer in ``0 .. C - 1``, a weight that is not
+    finite and > 0, and a value that is negative or not finite (Bernoulli: not 0 or 1)."""
+    lim = nb_limits()
+    C_ = int(num_classes)
+    if not 2 <= C_ <= lim["max_classes"]:
+        raise ValueError(f"Naive Bayes supports 2 .. {lim['max_classes']} classes, got {C_}")
+    indptr, idx, val = _csr(vc)
+    dev, F = indptr.device, int(vc.size)
+    y = torch.as_tensor(labels).to(device=dev, dtype=torch.float64).contiguous()
+    w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+    slot_of = hot_feat = None
+    if dev.type == "cuda":
+        hot_feat = nb_hot_set(indptr, idx, val, F, C_) if hot is None else \
+            torch.as_tensor(hot, dtype=torch.int32, device=dev).reshape(-1)
+        slot_of, hot_feat = nb_hot_tables(hot_feat, F, C_)
+    out = torch.zeros(C_ * F + 2 * C_ + 1, dtype=torch.int64, device=dev)
+    native.lib().nb_sums(indptr, idx, val, y, w, C_, F, int(k), int(kw), bool(bernoulli), slot_of, hot_feat, out,
+                         int(chunk_rows), threads)
+    host = out.cpu()                                   # the flag travels with the sums
+    if int(host[-1]):
+        _nb_raise(idx, val, y, w, C_, F, bool(bernoulli))
+    S = host[:C_ * F].view(C_, F)
+    return S, host[C_ * F:C_ * F + C_], host[C_ * F + C_:C_ * F + 2 * C_]
+
+
+def _nb_raise(idx, val, y, w, C_: int, F: int, bernoulli: bool) -> None:
+    """Name the bad input behind the pass's flag word (the slow path: only taken on an error)."""
+    if not bool(torch.all((y >= 0) & (y < C_) & (y == torch.floor(y)))):
+        raise ValueError(f"Naive Bayes labels must be integers in 0 .. {C_ - 1}")
+    if w is not None and not bool(torch.all(torch.isfinite(w) & (w > 0))):
+        raise ValueError("Naive Bayes weights must be finite and > 0")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
+        raise ValueError("feature index outside the feature space")
+    if bernoulli:
+        raise ValueError("Bernoulli Naive Bayes requires feature values 0 or 1")
+    raise ValueError("Multinomial Naive Bayes requires finite, non-negative feature values")
 
 
 def sim_limits() -> dict:

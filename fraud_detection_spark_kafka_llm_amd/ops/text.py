@@ -207,6 +207,28 @@ class LinearScorer(_DeviceCached):
         return self._cached(device, lambda d: torch.from_numpy(self.w).to(d))
 
 
+class ClassLinearScorer(_DeviceCached):
+    """``C`` linear class scores ``x . W[:, c] + b[c]`` (fp64): ``W`` feature-major ``[F, C]``, so
+    one gather brings every class of an entry (``csrc/nb_kernels.hip::nb_score_kernel``)."""
+
+    def __init__(self, W: np.ndarray, b: np.ndarray):
+        self.W = np.ascontiguousarray(W, dtype=np.float64)
+        self.b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        if self.W.ndim != 2 or self.W.shape[1] != self.b.size:
+            raise ValueError("W is [F, C] and b [C]")
+
+    @property
+    def num_classes(self) -> int:
+        return int(self.b.size)
+
+    def tensors(self, device, size: Optional[int] = None) -> tuple:
+        """(W, b) on ``device``; ``size`` > F pads W with rows of zeros (features the model lacks)."""
+        W, b = self._cached(device, lambda d: (torch.from_numpy(self.W).to(d), torch.from_numpy(self.b).to(d)))
+        if size is not None and size > W.shape[0]:
+            W = torch.cat([W, torch.zeros((size - W.shape[0], W.shape[1]), dtype=torch.float64, device=W.device)])
+        return W, b
+
+
 class TreeArrays(_DeviceCached):
     """Flattened ensemble (see ``fdx::TreeEnsemble``). ``K`` leaf values per node."""
 

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from .data import synth
-from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, NGram, Pipeline, PipelineModel,
+from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, NaiveBayes, NGram, Pipeline, PipelineModel,
                  RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
 from .ml.evaluation import evaluate_all
 from .ml.xgboost import SparkXGBClassifier
@@ -176,6 +176,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--model-path", default="fraud_detection_model")
     ap.add_argument("--no-plots", action="store_true")
     ap.add_argument("--ngram", type=int, default=1, help="insert an NGram(n) stage after the stop-word remover")
+    ap.add_argument("--naive-bayes", action="store_true", help="also train Spark's multinomial NaiveBayes")
     Config.add_cli_args(ap)          # --num-trees, --max-depth, --vocab-size, --seed, --device, --config ...
     args = ap.parse_args(argv)
     cfg = Config.from_cli(args)
@@ -191,8 +192,10 @@ def main(argv=None) -> dict:
         print(f"Training: {train_df.count()}")
         print(f"Validation: {val_df.count()}")
         print(f"Test: {test_df.count()}")
-        models = train_models(train_df, build_feature_pipeline(args.vocab_size, args.ngram),
-                              make_classifiers(args.num_trees, args.max_depth, args.seed))
+        classifiers = make_classifiers(args.num_trees, args.max_depth, args.seed)
+        if args.naive_bayes:
+            classifiers["NaiveBayes"] = NaiveBayes(featuresCol="features", labelCol="labels")
+        models = train_models(train_df, build_feature_pipeline(args.vocab_size, args.ngram), classifiers)
         results = {name: evaluate_model(m, {"Validation": val_df, "Test": test_df}) for name, m in models.items()}
         print("\nModel Evaluation Results:")
         for name, res in results.items():
