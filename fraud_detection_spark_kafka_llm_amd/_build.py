@@ -274,6 +274,26 @@ def build_nb_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     return out
 
 
+def build_mlr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/mlr_selftest.cpp`` + the multinomial logistic-regression host twin (``mlr_cpu.cpp``, and
+    ``nb_cpu.cpp`` for the class scores the margins must equal) as a standalone executable under
+    AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_nb_selftest`` (host code only,
+    one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("mlr_selftest_asan" if sanitize else "mlr_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "mlr_selftest_unity.cpp"
+    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in ("nb_cpu.cpp", "mlr_cpu.cpp"))
+                     + f'#include "{CSRC / "tests" / "mlr_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -292,7 +312,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the top-k cosine retrieval host twins")
     ap.add_argument("--nb-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the Naive Bayes host twins")
+    ap.add_argument("--mlr-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the multinomial logistic-regression host twin")
     args = ap.parse_args(argv)
+    if args.mlr_selftest:
+        return subprocess.run([str(build_mlr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.nb_selftest:
         return subprocess.run([str(build_nb_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.sim_selftest:

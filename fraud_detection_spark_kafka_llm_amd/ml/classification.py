@@ -158,21 +158,36 @@ class _LRParams(_PredictorParams):
 
 @register("org.apache.spark.ml.classification.LogisticRegression")
 class LogisticRegression(_LRParams, Estimator):
+    """Spark's ``LogisticRegression``. ``family="binomial"`` (or ``"auto"`` on labels in {0, 1}) fits
+    one coefficient row by L-BFGS / OWL-QN; ``family="multinomial"`` (or ``"auto"`` on labels
+    ``0 .. C - 1`` with ``C > 2``) fits ``C <= 8`` rows with an L2 penalty on the fused fixed-point
+    pass of ``models/lr.py::train_multinomial_logistic_regression``."""
     _uid_prefix = "LogisticRegression"
 
     def _fit(self, frame: Frame) -> "LogisticRegressionModel":
-        from ..models.lr import train_logistic_regression
+        from ..models.lr import label_maximum, train_logistic_regression, train_multinomial_logistic_regression
 
-        if self.getOrDefault("family") == "multinomial":
-            raise NotImplementedError("multinomial logistic regression is not supported")
+        family = self.getOrDefault("family")
+        if family not in ("auto", "binomial", "multinomial"):
+            raise ValueError(f"unknown LogisticRegression family {family!r}")
         vc = frame.column(self.getFeaturesCol())
         y = frame.column(self.getLabelCol())
         w = frame.column(self.getWeightCol()) if self.isSet("weightCol") else None
-        coef, intercept, history = train_logistic_regression(
-            vc, y, weights=w, max_iter=self.getMaxIter(), tol=self.getTol(), reg_param=self.getRegParam(),
-            elastic_net=self.getElasticNetParam(), fit_intercept=self.getFitIntercept(),
-            standardization=self.getStandardization())
-        m = LogisticRegressionModel(coef, intercept, uid=self.uid)
+        kw = dict(weights=w, max_iter=self.getMaxIter(), tol=self.getTol(), reg_param=self.getRegParam(),
+                  elastic_net=self.getElasticNetParam(), fit_intercept=self.getFitIntercept(),
+                  standardization=self.getStandardization())
+        if family != "multinomial":
+            ymax = label_maximum(y)
+            if family == "binomial" and ymax > 1:
+                raise ValueError(f"family='binomial' needs labels in {{0, 1}}, the largest label is {ymax:g}")
+            if family == "auto" and ymax > 1:
+                family = "multinomial"
+        if family == "multinomial":
+            coef, intercepts, history = train_multinomial_logistic_regression(vc, y, **kw)
+            m = LogisticRegressionModel(coefficientMatrix=coef, interceptVector=intercepts, uid=self.uid)
+        else:
+            coef, intercept, history = train_logistic_regression(vc, y, **kw)
+            m = LogisticRegressionModel(coef, intercept, uid=self.uid)
         m._paramMap.update(self._paramMap)
         m.objectiveHistory = history
         return m
@@ -180,25 +195,99 @@ class LogisticRegression(_LRParams, Estimator):
 
 @register("org.apache.spark.ml.classification.LogisticRegressionModel")
 class LogisticRegressionModel(_LRParams, ClassificationModelBase):
+    """A binomial model holds one coefficient row and one intercept; a multinomial model holds
+    ``numClasses`` rows (``coefficientMatrix`` [C, F], ``interceptVector`` [C]). For the latter
+    ``rawPrediction`` is the ``C`` class scores of ``ops.sparse.score_csr`` (``nb_score``),
+    ``probability`` their max-subtracted softmax and ``prediction`` the first argmax (``threshold``
+    is ignored, as in Spark). A 2-row model also serves through the single-launch paths as the
+    margin ``raw_1 - raw_0``, exactly as a binary ``NaiveBayesModel`` does."""
     _uid_prefix = "LogisticRegression"
 
-    def __init__(self, coefficients=None, intercept: float = 0.0, **kw):
+    def __init__(self, coefficients=None, intercept: float = 0.0, coefficientMatrix=None, interceptVector=None,
+                 **kw):
         super().__init__(**kw)
-        self.coefficients = np.asarray(coefficients if coefficients is not None else [], dtype=np.float64)
-        self.intercept = float(intercept)
+        if coefficientMatrix is not None:
+            self._set_model(coefficientMatrix, interceptVector)
+        else:
+            self._set_model(np.asarray(coefficients if coefficients is not None else [], dtype=np.float64)[None, :],
+                            [float(intercept)])
         self.objectiveHistory: list = []
-        self._scorer = None
+
+    def _set_model(self, matrix, intercepts) -> None:
+        self._W = np.ascontiguousarray(matrix, dtype=np.float64)
+        if self._W.ndim != 2 or self._W.shape[0] < 1:
+            raise ValueError("coefficientMatrix is [numClasses, numFeatures] (one row for a binomial model)")
+        self._b = np.zeros(self._W.shape[0]) if intercepts is None else \
+            np.ascontiguousarray(intercepts, dtype=np.float64).reshape(-1)
+        if self._b.size != self._W.shape[0]:
+            raise ValueError("interceptVector needs one entry per row of coefficientMatrix")
+        self._scorer = self._class_scorer = None
+
+    @property
+    def isMultinomial(self) -> bool:  # noqa: N802
+        return self._W.shape[0] > 1
+
+    @property
+    def numClasses(self) -> int:  # noqa: N802
+        return int(self._W.shape[0]) if self.isMultinomial else 2
 
     @property
     def numFeatures(self) -> int:  # noqa: N802
-        return int(self.coefficients.size)
+        return int(self._W.shape[1])
+
+    @property
+    def coefficientMatrix(self) -> np.ndarray:  # noqa: N802
+        return self._W
+
+    @property
+    def interceptVector(self) -> np.ndarray:  # noqa: N802
+        return self._b
+
+    @property
+    def coefficients(self) -> np.ndarray:
+        if self.isMultinomial:
+            raise ValueError("a multinomial model has no single coefficient vector: use coefficientMatrix")
+        return self._W[0]
+
+    @property
+    def intercept(self) -> float:
+        if self.isMultinomial:
+            raise ValueError("a multinomial model has no single intercept: use interceptVector")
+        return float(self._b[0])
+
+    def class_scorer(self) -> ClassLinearScorer:
+        """The rows as ``C`` linear class scores (``W`` feature-major); multinomial models only."""
+        if not self.isMultinomial:
+            raise ValueError("a binomial model scores one margin: use scorer()")
+        if self._class_scorer is None:
+            self._class_scorer = ClassLinearScorer(np.ascontiguousarray(self._W.T), self._b)
+        return self._class_scorer
 
     def scorer(self) -> LinearScorer:
+        """The margin as one ``LinearScorer``; of a 2-row model ``raw_1 - raw_0`` (differences taken
+        once in fp64)."""
+        if self.numClasses != 2:
+            raise ValueError(f"the single-launch and streaming paths score binary models only; this logistic "
+                             f"regression model has {self.numClasses} classes (use transform / predictRaw)")
         if self._scorer is None:
-            self._scorer = LinearScorer(self.coefficients, self.intercept)
+            self._scorer = LinearScorer(self._W[1] - self._W[0], float(self._b[1] - self._b[0])) \
+                if self.isMultinomial else LinearScorer(self.coefficients, self.intercept)
         return self._scorer
 
     def postprocess(self, raw: torch.Tensor):
+        if self.isMultinomial:
+            if raw.shape[1] == 1:                    # the serving paths' margin raw_1 - raw_0
+                if self.numClasses != 2:
+                    raise ValueError("a margin describes a binary model")
+                m = raw[:, 0]
+                rp = torch.stack([torch.zeros_like(m), m], dim=1)
+                prob = 1.0 / (1.0 + torch.exp(-torch.stack([-m, m], dim=1)))
+                return rp, prob, _argmax_prediction(prob)
+            if raw.shape[1] != self.numClasses:
+                raise ValueError(f"expected [N, {self.numClasses}] class scores or an [N, 1] margin")
+            e = torch.exp(raw - raw.max(dim=1, keepdim=True).values)
+            prob = e / e.sum(dim=1, keepdim=True)
+            return raw, prob, _argmax_prediction(prob)
         m = raw[:, 0]
         rp = torch.stack([-m, m], dim=1)
         prob = 1.0 / (1.0 + torch.exp(-rp))           # Spark raw2probability on [-m, m]
@@ -207,7 +296,7 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
 
     def contributions(self, features) -> VectorColumn:
         """Every row stores its own entries ``w_f * x_f``, then the intercept at ``numFeatures``."""
-        if self.getOrDefault("family") == "multinomial":
+        if self.isMultinomial or self.getOrDefault("family") == "multinomial":
             raise NotImplementedError("contributions of multinomial logistic regression are not supported")
         vc = self._features_column(features)
         if vc.size != self.numFeatures:
@@ -215,31 +304,73 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
         return _linear_contributions(vc, self.scorer().weights(vc.device), self.intercept, self.numFeatures)
 
     def postprocess_numpy(self, raw: np.ndarray):
+        if self.isMultinomial and raw.shape[1] != 1:
+            return super().postprocess_numpy(raw)
         p = np.exp(-raw[:, 0])
         np.add(p, 1.0, out=p)
         np.reciprocal(p, out=p)
+        if self.isMultinomial:                       # first argmax of [1 - p, p]
+            return (p > 1.0 - p).astype(np.float64), p
         return (p > self.getThreshold()).astype(np.float64), p
+
+    def _score(self, vc: VectorColumn) -> torch.Tensor:
+        from ..ops.sparse import score_csr
+
+        return score_csr(vc, self.class_scorer() if self.isMultinomial else self.scorer())
+
+    def _transform(self, frame: Frame) -> Frame:
+        if not self.isMultinomial:
+            return super()._transform(frame)
+        return self.attach_outputs(frame, self._score(self._features_column(frame)))
+
+    def predictRaw(self, features) -> DenseVector:  # noqa: N802
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self.postprocess(self._score(vc))[0][0].cpu().numpy())
+
+    def predictProbability(self, features) -> DenseVector:  # noqa: N802
+        if not self.isMultinomial:
+            return super().predictProbability(features)
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self.postprocess(self._score(vc))[1][0].cpu().numpy())
+
+    def predict(self, features) -> float:
+        if not self.isMultinomial:
+            return super().predict(features)
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return float(self.postprocess(self._score(vc))[2][0])
 
     def _metadata_extra(self):
         return None
 
     def _save_data(self, path) -> None:
-        sf.write_data_parquet(path, [
-            sf.Field.simple("numClasses", "integer"), sf.Field.simple("numFeatures", "integer"),
-            sf.Field.vector("interceptVector"), sf.Field.matrix("coefficientMatrix"),
-            sf.Field.simple("isMultinomial", "boolean")],
-            [{"numClasses": 2, "numFeatures": self.numFeatures, "interceptVector": sf.dense_vector([self.intercept]),
-              "coefficientMatrix": sf.sparse_matrix_row_major(self.coefficients[None, :]), "isMultinomial": False}])
+        fields = [sf.Field.simple("numClasses", "integer"), sf.Field.simple("numFeatures", "integer"),
+                  sf.Field.vector("interceptVector"), sf.Field.matrix("coefficientMatrix"),
+                  sf.Field.simple("isMultinomial", "boolean")]
+        if not self.isMultinomial:
+            sf.write_data_parquet(path, fields, [
+                {"numClasses": 2, "numFeatures": self.numFeatures, "interceptVector": sf.dense_vector([self.intercept]),
+                 "coefficientMatrix": sf.sparse_matrix_row_major(self.coefficients[None, :]), "isMultinomial": False}])
+            return
+        # Spark's Matrix.compressed: the smaller of the dense and the row-major sparse form (12 bytes
+        # per stored entry against 8 per cell); a -0.0 survives only the dense form
+        W = self._W
+        nnz = int(np.count_nonzero(W))
+        sparse = 12 * nnz + 4 * (W.shape[0] + 1) < 8 * W.size and not bool(np.any(np.signbit(W) & (W == 0)))
+        sf.write_data_parquet(path, fields, [
+            {"numClasses": self.numClasses, "numFeatures": self.numFeatures,
+             "interceptVector": sf.dense_vector(self._b),
+             "coefficientMatrix": sf.sparse_matrix_row_major(W) if sparse else sf.dense_matrix(W),
+             "isMultinomial": True}])
 
     def _load_data(self, path, md) -> None:
         row = sf.read_data_parquet(path).to_pylist()[0]
+        coef = sf.decode_matrix(row["coefficientMatrix"]).astype(np.float64)
+        icpt = sf.decode_vector(row["interceptVector"])
         if row.get("isMultinomial"):
-            raise NotImplementedError("multinomial logistic regression models are not supported")
-        coef = sf.decode_matrix(row["coefficientMatrix"])
-        self.coefficients = coef[0].astype(np.float64)
-        self.intercept = float(sf.decode_vector(row["interceptVector"])[0])
+            self._set_model(coef, icpt)
+        else:
+            self._set_model(coef[:1], [float(icpt[0])])
         self.objectiveHistory = []
-        self._scorer = None
 
 
 # ============================================================================ trees

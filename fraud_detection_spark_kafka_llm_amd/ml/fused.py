@@ -14,7 +14,7 @@ import torch
 
 from ..ops.text import NGRAM_MAX, FeatureSpec, PackedText, featurize_score
 from ..utils.config import default_device
-from .classification import ClassificationModelBase, NaiveBayesModel
+from .classification import ClassificationModelBase, LogisticRegressionModel, NaiveBayesModel
 from .feature import CountVectorizerModel, HashingTF, IDFModel, NGram, StopWordsRemover, Tokenizer, native_vectors
 from .frame import Frame, Lazy, TextColumn, TokenColumn
 from .linalg import VectorColumn
@@ -141,7 +141,7 @@ class _Plan:
                 w = idf.idf_tensor(v.device)
                 return VectorColumn.scaled_counts(vc.size, ip, ix, v, w)
             frame = frame.withColumn(idf.getOutputCol(), Lazy(_idf, n))
-        if isinstance(model, NaiveBayesModel):
+        if isinstance(model, NaiveBayesModel) or (isinstance(model, LogisticRegressionModel) and model.isMultinomial):
             # C class scores: the fused launch's CSR (the lazy feature column above: want_csr, no
             # scorer) scored by score_csr's nb_score, so rawPrediction is Spark's and the outputs
             # equal the staged transform bit for bit

@@ -18,6 +18,10 @@ With ``regParam > 0`` and ``elasticNetParam > 0`` the objective gains the L1 ter
 ``regParam * (alpha * ||beta||_1 + (1 - alpha)/2 * ||beta||^2)`` and the trainer is OWL-QN (``_train_owlqn``)
 on the fused kernels of ``csrc/lr_kernels.hip``: coefficients that leave their orthant are exactly 0.0.
 Every other parameter pair runs the L-BFGS body below unchanged.
+
+``train_multinomial_logistic_regression`` fits ``C`` coefficient rows (softmax, L2 penalty) with the same
+L-BFGS loop; one evaluation is the fused ``ops.sparse.mlr_eval`` pass (``csrc/mlr_kernels.hip``), whose
+gradient and loss are exact int64 fixed-point sums, so no transposed matrix is built.
 """
 from __future__ import annotations
 
@@ -29,7 +33,10 @@ import torch
 
 from ..ml.linalg import VectorColumn
 from ..ops import native
-from ..ops.sparse import lr_forward, lr_owlqn_step, lr_pseudo_grad, spmv
+from ..ops.sparse import _csr as sparse_csr
+from ..ops.sparse import (lr_forward, lr_owlqn_step, lr_pseudo_grad, mlr_eval, mlr_limits, mlr_scale_exponents,
+                          nb_hot_set, nb_hot_tables, spmv)
+from ..parallel import dist as D
 from ..parallel.dist import Collectives
 from ..utils.config import default_device
 
@@ -46,33 +53,9 @@ def transpose_csr(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, nu
     return t_indptr, rows[order].contiguous(), val[order].contiguous()
 
 
-def train_logistic_regression(features, labels, weights=None, max_iter: int = 100, tol: float = 1e-6,
-                              reg_param: float = 0.0, elastic_net: float = 0.0, fit_intercept: bool = True,
-                              standardization: bool = True, device=None, history_size: int = 10):
-    if not 0.0 <= elastic_net <= 1.0:
-        raise ValueError(f"elastic_net must be in [0, 1], got {elastic_net}")
-    if reg_param < 0:
-        raise ValueError(f"reg_param must be >= 0, got {reg_param}")
-    dev = torch.device(device) if device is not None else default_device()
-    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
-    vc = vc.to(dev)
-    indptr, idx, val = vc.csr()
-    idx = idx.to(torch.int32).contiguous()
-    val = val.to(torch.float64).contiguous()
-    F = vc.size
-    n = len(vc)
-    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
-                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64)
-    w = torch.ones(n, dtype=torch.float64, device=dev) if weights is None else \
-        torch.as_tensor(np.asarray(weights, dtype=np.float64)).to(dev)
-    coll = Collectives()
-    wsum = float(coll.sum(w.sum().reshape(1))[0])
-    t_indptr, t_idx, t_val = transpose_csr(indptr, idx, val, F)
-
-    def xt(v: torch.Tensor, vals: Optional[torch.Tensor] = None) -> torch.Tensor:     # X^T v, fixed order
-        return spmv(t_indptr, t_idx, t_val if vals is None else vals, v)
-
-    # feature scaling (sample std over all ranks)
+def _feature_scale(xt, t_val, w, wsum, coll, F: int, standardization: bool) -> torch.Tensor:
+    """``1 / std`` of every feature (sample std over all ranks, constant features 0) with
+    ``standardization``, ones without; ``xt(v, vals)`` is the fixed-order ``X^T v``."""
     if standardization:
         s1 = coll.sum(xt(w))
         s2 = coll.sum(xt(w, t_val * t_val))
@@ -81,31 +64,14 @@ def train_logistic_regression(features, labels, weights=None, max_iter: int = 10
         std = torch.sqrt(torch.clamp(var, min=0.0))
         scale = torch.where(std > 0, 1.0 / torch.where(std > 0, std, torch.ones_like(std)), torch.zeros_like(std))
     else:
-        scale = torch.ones(F, dtype=torch.float64, device=dev)
+        scale = torch.ones(F, dtype=torch.float64, device=w.device)
+    return scale
 
-    def fg(theta: torch.Tensor):
-        beta, b = theta[:F], theta[F]
-        m = spmv(indptr, idx, val, scale * beta) + (b if fit_intercept else 0.0)
-        # stable log(1 + e^m) - y m
-        loss_i = torch.clamp(m, min=0) - m * y + torch.log1p(torch.exp(-torch.abs(m)))
-        r = w * (torch.sigmoid(m) - y)
-        parts = torch.cat([(w * loss_i).sum().reshape(1), r.sum().reshape(1), xt(r)])
-        parts = coll.sum(parts)
-        loss = parts[0] / wsum + 0.5 * reg_param * torch.dot(beta, beta)
-        g = torch.empty_like(theta)
-        g[:F] = scale * parts[2:] / wsum + reg_param * beta
-        g[F] = parts[1] / wsum if fit_intercept else 0.0
-        return float(loss), g
 
-    theta = torch.zeros(F + 1, dtype=torch.float64, device=dev)
-    if fit_intercept:
-        p = float(coll.sum((w * y).sum().reshape(1))[0]) / wsum
-        if 0 < p < 1:
-            theta[F] = math.log(p / (1 - p))
-    if reg_param > 0 and elastic_net > 0:
-        return _train_owlqn((indptr, idx, val), (t_indptr, t_idx, t_val), y, w, wsum, scale, theta, coll,
-                            reg_param * elastic_net, reg_param * (1.0 - elastic_net), max_iter, tol, fit_intercept,
-                            history_size)
+def _lbfgs(fg, theta: torch.Tensor, max_iter: int, tol: float, history_size: int):
+    """L-BFGS on ``fg(theta) -> (loss, gradient)`` from ``theta``: ``history_size`` correction pairs,
+    Armijo halving, stops after ``max_iter`` iterations, when the relative improvement falls below
+    ``tol`` or the gradient norm below 1e-9. Returns ``(theta, objective history)``."""
     loss, g = fg(theta)
     history = [loss]
     S, Y = [], []
@@ -154,6 +120,61 @@ def train_logistic_regression(features, labels, weights=None, max_iter: int = 10
         history.append(loss)
         if abs(improvement) < tol or float(torch.linalg.vector_norm(g)) < 1e-9:
             break
+    return theta, history
+
+
+def train_logistic_regression(features, labels, weights=None, max_iter: int = 100, tol: float = 1e-6,
+                              reg_param: float = 0.0, elastic_net: float = 0.0, fit_intercept: bool = True,
+                              standardization: bool = True, device=None, history_size: int = 10):
+    if not 0.0 <= elastic_net <= 1.0:
+        raise ValueError(f"elastic_net must be in [0, 1], got {elastic_net}")
+    if reg_param < 0:
+        raise ValueError(f"reg_param must be >= 0, got {reg_param}")
+    dev = torch.device(device) if device is not None else default_device()
+    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
+    vc = vc.to(dev)
+    indptr, idx, val = vc.csr()
+    idx = idx.to(torch.int32).contiguous()
+    val = val.to(torch.float64).contiguous()
+    F = vc.size
+    n = len(vc)
+    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
+                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64)
+    w = torch.ones(n, dtype=torch.float64, device=dev) if weights is None else \
+        torch.as_tensor(np.asarray(weights, dtype=np.float64)).to(dev)
+    coll = Collectives()
+    wsum = float(coll.sum(w.sum().reshape(1))[0])
+    t_indptr, t_idx, t_val = transpose_csr(indptr, idx, val, F)
+
+    def xt(v: torch.Tensor, vals: Optional[torch.Tensor] = None) -> torch.Tensor:     # X^T v, fixed order
+        return spmv(t_indptr, t_idx, t_val if vals is None else vals, v)
+
+    scale = _feature_scale(xt, t_val, w, wsum, coll, F, standardization)
+
+    def fg(theta: torch.Tensor):
+        beta, b = theta[:F], theta[F]
+        m = spmv(indptr, idx, val, scale * beta) + (b if fit_intercept else 0.0)
+        # stable log(1 + e^m) - y m
+        loss_i = torch.clamp(m, min=0) - m * y + torch.log1p(torch.exp(-torch.abs(m)))
+        r = w * (torch.sigmoid(m) - y)
+        parts = torch.cat([(w * loss_i).sum().reshape(1), r.sum().reshape(1), xt(r)])
+        parts = coll.sum(parts)
+        loss = parts[0] / wsum + 0.5 * reg_param * torch.dot(beta, beta)
+        g = torch.empty_like(theta)
+        g[:F] = scale * parts[2:] / wsum + reg_param * beta
+        g[F] = parts[1] / wsum if fit_intercept else 0.0
+        return float(loss), g
+
+    theta = torch.zeros(F + 1, dtype=torch.float64, device=dev)
+    if fit_intercept:
+        p = float(coll.sum((w * y).sum().reshape(1))[0]) / wsum
+        if 0 < p < 1:
+            theta[F] = math.log(p / (1 - p))
+    if reg_param > 0 and elastic_net > 0:
+        return _train_owlqn((indptr, idx, val), (t_indptr, t_idx, t_val), y, w, wsum, scale, theta, coll,
+                            reg_param * elastic_net, reg_param * (1.0 - elastic_net), max_iter, tol, fit_intercept,
+                            history_size)
+    theta, history = _lbfgs(fg, theta, max_iter, tol, history_size)
     coef = (scale * theta[:F]).cpu().numpy()
     intercept = float(theta[F]) if fit_intercept else 0.0
     return coef, intercept, history
@@ -281,3 +302,162 @@ def _train_owlqn(csr, t_csr, y, w, wsum, scale, theta, coll, l1, l2, max_iter, t
     coef = xs.cpu().numpy()        # scale * x[:F]: a coefficient left at exactly 0.0 stays 0.0
     intercept = float(x[F]) if fit_intercept else 0.0
     return coef, intercept, history
+
+
+# ============================================================================ multinomial
+def label_maximum(labels, device=None) -> float:
+    """Largest label over all ranks (one MAX all-reduce under data parallelism): ``family="auto"``
+    is multinomial iff it exceeds 1."""
+    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
+                        np.asarray([float(v) for v in labels])).to(torch.float64).reshape(-1)
+    m = y.max().reshape(1) if y.numel() else y.new_zeros(1)
+    if D.is_dist():
+        m = D.all_reduce_max(m.to(torch.device(device) if device is not None else default_device()))
+    return float(m[0])
+
+
+def _mlr_raise(idx, val, y, w, C: int, F: int) -> None:
+    """Name the bad input behind the pass's flag word (the slow path: only taken on an error)."""
+    if not bool(torch.all((y >= 0) & (y < C) & (y == torch.floor(y)))):
+        raise ValueError(f"multinomial logistic regression labels must be integers in 0 .. {C - 1}")
+    if w is not None and not bool(torch.all(torch.isfinite(w) & (w >= 0))):
+        raise ValueError("multinomial logistic regression weights must be finite and >= 0")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
+        raise ValueError("feature index outside the feature space")
+    raise ValueError("multinomial logistic regression requires finite feature values")
+
+
+# counters of the last multinomial fit: read by the profile note and the micro-benchmark only
+MLR_STATS = {"evaluations": 0, "iterations": 0, "k": 0, "kl": 0}
+
+
+def train_multinomial_logistic_regression(features, labels, weights=None, max_iter: int = 100, tol: float = 1e-6,
+                                          reg_param: float = 0.0, elastic_net: float = 0.0,
+                                          fit_intercept: bool = True, standardization: bool = True, device=None,
+                                          history_size: int = 10, hot=None, chunk_rows: int = 0, threads: int = 0):
+    """Spark's multinomial ``LogisticRegression`` with an L2 penalty: minimises
+    ``(1/W) sum_i w_i [logsumexp_c(m_ic) - m_{i, y_i}] + regParam/2 |B|_F^2`` with
+    ``m_ic = b_c + sum_j x_ij s_j B_cj`` by the L-BFGS loop of the binomial route on ``[B.ravel(), b]``.
+    One evaluation is one fused ``ops.sparse.mlr_eval`` pass whose reduced quantities are exact int64
+    sums, so for given residuals the gradient and the loss depend on no order of summation; under data
+    parallelism an evaluation all-reduces that one int64 block. Labels are integers in ``0 .. C - 1``
+    with ``C = max label + 1`` (2 .. 8). Returns ``(coefficientMatrix [C, F], interceptVector [C],
+    objective history)``; the coefficients are centred over the classes when ``regParam == 0`` and the
+    intercepts always, as Spark does. ``hot`` (feature ids summed in LDS on the device, ``None`` =
+    ``nb_hot_set``), ``chunk_rows`` and ``threads`` change the speed only."""
+    if not 0.0 <= elastic_net <= 1.0:
+        raise ValueError(f"elastic_net must be in [0, 1], got {elastic_net}")
+    if reg_param < 0:
+        raise ValueError(f"reg_param must be >= 0, got {reg_param}")
+    if reg_param > 0 and elastic_net > 0:
+        raise NotImplementedError("multinomial logistic regression supports elasticNetParam = 0 only "
+                                  "(no L1 part)")
+    dev = torch.device(device) if device is not None else default_device()
+    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
+    vc = vc.to(dev)
+    indptr, idx, val = sparse_csr(vc)
+    F, n = int(vc.size), len(vc)
+    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
+                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64).contiguous()
+    w = None if weights is None else torch.as_tensor(
+        weights if isinstance(weights, (torch.Tensor, np.ndarray)) else np.asarray(weights, dtype=np.float64)
+    ).to(device=dev, dtype=torch.float64).contiguous()
+    if y.numel() != n or (w is not None and w.numel() != n):
+        raise ValueError("labels and weights need one entry per row")
+    # (largest label, - smallest label, largest weight, - smallest weight, largest |value|): one small
+    # copy, MAX over the ranks (a NaN survives every maximum)
+    zero, one = y.new_zeros(()), y.new_ones(())
+    stats = torch.stack([y.max() if n else zero, -y.min() if n else zero,
+                         w.max() if w is not None and n else one, -w.min() if w is not None and n else -one,
+                         val.abs().max().to(torch.float64) if val.numel() else zero])
+    rows = torch.tensor([n], dtype=torch.int64, device=dev)
+    if D.is_dist():
+        stats = D.all_reduce_max(stats)
+        rows = D.all_reduce_sum(rows)
+    ymax, ymin_neg, wmax, wmin_neg, vmax = (float(v) for v in stats.cpu())
+    n_global = int(rows[0])
+    lim = mlr_limits()
+    if not (math.isfinite(ymax) and math.isfinite(ymin_neg)) or ymin_neg > 0 or ymax != math.floor(ymax):
+        raise ValueError("multinomial logistic regression labels must be integers in 0 .. C - 1")
+    C = max(int(ymax) + 1, 2)
+    if C > lim["max_classes"]:
+        raise ValueError(f"multinomial logistic regression supports at most {lim['max_classes']} classes, "
+                         f"the labels name {C}")
+    if not (math.isfinite(wmax) and math.isfinite(wmin_neg)) or wmin_neg > 0:
+        raise ValueError("multinomial logistic regression weights must be finite and >= 0")
+    if not math.isfinite(vmax):
+        raise ValueError("multinomial logistic regression requires finite feature values")
+    k, kl = mlr_scale_exponents(wmax, vmax, n_global)
+    coll = Collectives()
+    w_rows = torch.ones(n, dtype=torch.float64, device=dev) if w is None else w
+    class_w = coll.sum(torch.stack([(w_rows * (y == c)).sum() for c in range(C)]))
+    wsum = float(coll.sum(w_rows.sum().reshape(1))[0])
+    if not wsum > 0:
+        raise ValueError("multinomial logistic regression needs a positive weight sum")
+    if standardization:
+        val64 = val.to(torch.float64)
+        t_indptr, t_idx, t_val = transpose_csr(indptr, idx, val64, F)
+
+        def xt(v: torch.Tensor, vals: Optional[torch.Tensor] = None) -> torch.Tensor:
+            return spmv(t_indptr, t_idx, t_val if vals is None else vals, v)
+
+        scale = _feature_scale(xt, t_val, w_rows, wsum, coll, F, True)
+        del t_indptr, t_idx, t_val, val64
+    else:
+        scale = _feature_scale(None, None, w_rows, wsum, coll, F, False)
+    hot_tables = (None, None)
+    if dev.type == "cuda":
+        hot_feat = nb_hot_set(indptr, idx, val, F, C) if hot is None else \
+            torch.as_tensor(hot, dtype=torch.int32, device=dev).reshape(-1)
+        hot_tables = nb_hot_tables(hot_feat, F, C)
+    inv_k = math.ldexp(1.0, -k)
+    stats_ = MLR_STATS
+    stats_.update(evaluations=0, iterations=0, k=k, kl=kl)
+
+    def fg(theta: torch.Tensor):
+        B, b = theta[:C * F].view(C, F), theta[C * F:]
+        XS = (scale.unsqueeze(1) * B.t()).contiguous()
+        res = mlr_eval(indptr, idx, val, XS, b.contiguous(), y, w, k, kl, hot_tables, chunk_rows=chunk_rows,
+                       check_extents=stats_["evaluations"] == 0, threads=threads)
+        block = coll.sum(res.block)
+        tail = block[-2:].cpu()
+        lossq, flag = int(tail[0]), int(tail[1])
+        if flag >> 32:
+            _mlr_raise(idx, val, y, w, C, F)
+        first = stats_["evaluations"] == 0
+        stats_["evaluations"] += 1
+        g = torch.empty_like(theta)
+        G = block[:F * C].view(F, C).to(torch.float64) * inv_k
+        g[:C * F].view(C, F).copy_(scale.unsqueeze(0) * G.t() / wsum + reg_param * B)
+        if fit_intercept:
+            g[C * F:] = block[F * C:F * C + C].to(torch.float64) * inv_k / wsum
+        else:
+            g[C * F:] = 0.0
+        if flag & 0xFFFFFFFF:       # a clamped row loss: the trial is rejected like an infinite objective
+            if first:
+                raise ValueError("multinomial logistic regression: a row's loss at the starting point is not "
+                                 f"below {int(lim['loss_cap'])} (margins out of range)")
+            return math.inf, g
+        loss = math.ldexp(float(lossq), -kl) / wsum + 0.5 * reg_param * float(torch.dot(theta[:C * F], theta[:C * F]))
+        return loss, g
+
+    theta = torch.zeros(C * F + C, dtype=torch.float64, device=dev)
+    if fit_intercept:
+        cw = class_w.cpu().numpy()
+        present = cw > 0
+        with np.errstate(divide="ignore"):
+            lp = np.log(cw / wsum)
+        lp[~present] = lp[present].min() - 1.0
+        theta[C * F:] = torch.from_numpy(lp - lp[present].mean()).to(dev)
+    theta, history = _lbfgs(fg, theta, max_iter, tol, history_size)
+    stats_["iterations"] = len(history) - 1
+    B = theta[:C * F].view(C, F).cpu().numpy().copy()
+    b = theta[C * F:].cpu().numpy().copy()
+    if fit_intercept:
+        b -= b.mean()
+    else:
+        b[:] = 0.0
+    if reg_param == 0:
+        B -= B.mean(axis=0, keepdims=True)
+    coef = scale.cpu().numpy()[None, :] * B
+    return coef, b, history

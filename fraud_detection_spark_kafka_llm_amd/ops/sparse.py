@@ -259,6 +259,87 @@ def _nb_raise(idx, val, y, w, C_: int, F: int, bernoulli: bool) -> None:
     raise ValueError("Multinomial Naive Bayes requires finite, non-negative feature values")
 
 
+def mlr_limits() -> dict:
+    """Structural constants of the multinomial logistic-regression kernel: those of ``nb_limits`` it
+    shares (``max_classes``, ``chunk_rows``, ``table_bytes``, ``max_table_bytes``, ``k_max``,
+    ``sum_bits``, wave and workgroup size), the loss cap (``loss_cap = 2^loss_bits``) and the two
+    halves of the flag word (``flag_clamped``, ``flag_bad_input``)."""
+    return dict(native.lib().mlr_limits())
+
+
+def mlr_scale_exponents(wmax: float, vmax: float, n_rows: int) -> tuple:
+    """``(k, kl)`` of ``mlr_eval`` for weights up to ``wmax``, absolute values up to ``vmax`` and
+    ``n_rows`` rows in all: ``k = min(k_max, sum_bits - n_rows.bit_length() - e)`` with
+    ``max(wmax max(vmax, 1), 1) < 2^e`` (a residual is at most its row's weight) and
+    ``kl = min(k_max, sum_bits - n_rows.bit_length() - e_w - loss_bits)`` with ``max(wmax, 1) < 2^e_w``
+    (``frexp``). Raises ``ValueError`` when an exponent is negative."""
+    lim = mlr_limits()
+    wmax, vmax = float(wmax), float(vmax)
+    if not (math.isfinite(wmax) and math.isfinite(vmax)) or wmax < 0 or vmax < 0:
+        raise ValueError(f"multinomial logistic regression needs finite values and finite, non-negative weights "
+                         f"(largest weight {wmax}, largest |value| {vmax})")
+    room = int(lim["sum_bits"]) - int(n_rows).bit_length()
+    k = min(int(lim["k_max"]), room - math.frexp(max(wmax * max(vmax, 1.0), 1.0))[1])
+    kl = min(int(lim["k_max"]), room - math.frexp(max(wmax, 1.0))[1] - int(lim["loss_bits"]))
+    if k < 0 or kl < 0:
+        raise ValueError(f"weights up to {wmax:g} and values up to {vmax:g} over {n_rows} rows do not fit the exact "
+                         f"{lim['sum_bits']}-bit sums of multinomial logistic regression")
+    return k, kl
+
+
+@dataclass
+class MlrBlock:
+    """The int64 block of one ``mlr_eval``: ``Gq`` [F, C] feature-major, ``gbq`` [C], ``lossq``, the
+    two flags, and the per-row outputs when they were asked for."""
+    block: torch.Tensor
+    F: int
+    C: int
+    margin: Optional[torch.Tensor] = None
+    R: Optional[torch.Tensor] = None
+    loss_row: Optional[torch.Tensor] = None
+
+    @property
+    def Gq(self) -> torch.Tensor:
+        return self.block[:self.F * self.C].view(self.F, self.C)
+
+    @property
+    def gbq(self) -> torch.Tensor:
+        return self.block[self.F * self.C:self.F * self.C + self.C]
+
+    @property
+    def lossq(self) -> int:
+        return int(self.block[-2])
+
+    @property
+    def clamped(self) -> bool:
+        return bool(int(self.block[-1]) & 0xFFFFFFFF)
+
+    @property
+    def bad_input(self) -> bool:
+        return bool(int(self.block[-1]) >> 32)
+
+
+def mlr_eval(indptr, idx, val, XS: torch.Tensor, b: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor],
+             k: int, kl: int, hot_tables: tuple = (None, None), want_rows: bool = False, chunk_rows: int = 0,
+             check_extents: bool = True, threads: int = 0) -> MlrBlock:
+    """One evaluation of multinomial logistic regression on a CSR (``val`` fp32 or fp64) in one fused
+    pass: margins bitwise ``score_csr(ClassLinearScorer(XS, b))``, the row terms of ``csrc/mlr.h``
+    and the exact int64 sums ``Gq[f, c] = sum rint(x_if r_ic 2^k)``, ``gbq[c] = sum rint(r_ic 2^k)``,
+    ``lossq = sum rint(w_i min(loss_i, 2048) 2^kl)``. ``XS`` is ``[F, C]`` fp64 feature-major.
+    ``hot_tables`` is ``nb_hot_tables(...)`` of the features summed in LDS on the device (the host
+    ignores it); like ``chunk_rows`` and ``threads`` it changes the speed only. The block stays on
+    the CSR's device; nothing is read back here, the caller tests the flags."""
+    dev = indptr.device
+    F, C_ = int(XS.shape[0]), int(XS.shape[1])
+    n = indptr.numel() - 1
+    slot_of, hot_feat = hot_tables if dev.type == "cuda" else (None, None)
+    out = torch.zeros(F * C_ + C_ + 2, dtype=torch.int64, device=dev)
+    rows = [torch.empty(s, dtype=torch.float64, device=dev) if want_rows else None for s in ((n, C_), (n, C_), (n,))]
+    native.lib().mlr_eval(indptr, idx, val, XS, b, y, w, int(k), int(kl), slot_of, hot_feat, out, rows[0], rows[1],
+                          rows[2], int(chunk_rows), bool(check_extents), threads)
+    return MlrBlock(out, F, C_, *rows)
+
+
 def sim_limits() -> dict:
     """Structural constants of the retrieval kernels: largest ``k``, distinct terms of a query held
     in LDS, corpus rows per workgroup chunk, queries per pass over a chunk, wave and workgroup size."""

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from .data import synth
-from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, NaiveBayes, NGram, Pipeline, PipelineModel,
-                 RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
+from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, LogisticRegression, NaiveBayes, NGram, Pipeline,
+                 PipelineModel, RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
 from .ml.evaluation import evaluate_all
 from .ml.xgboost import SparkXGBClassifier
 from .ops.sparse import term_presence_by_label
@@ -144,6 +144,39 @@ def evaluate_model(model: PipelineModel, datasets: dict) -> dict:
     return out
 
 
+def integer_codes(frame: Frame, col: str) -> np.ndarray:
+    """The column ``col`` as float64 class codes; its values must read as integers >= 0."""
+    c = frame.column(col)
+    vals = c.strings if hasattr(c, "strings") else (c.cpu().numpy() if isinstance(c, torch.Tensor) else list(c))
+    try:
+        codes = np.array([float(str(v).strip()) for v in vals], dtype=np.float64)
+    except ValueError:
+        raise ValueError(f"column {col!r} is not integer-coded") from None
+    if codes.size and not np.all((codes >= 0) & (codes == np.floor(codes))):
+        raise ValueError(f"column {col!r} is not integer-coded")
+    return codes
+
+
+def fit_multinomial_lr(feature_stages: list, label_col: str, datasets: dict, reg_param: float = 0.01) -> dict:
+    """Multinomial ``LogisticRegression`` on the fitted feature stages with ``label_col`` as the class
+    (``datasets`` holds the ``Train`` frame and the frames to score): accuracy per dataset."""
+    frames = {}
+    for name, df in datasets.items():
+        cur = df
+        for s in feature_stages:
+            cur = s.transform(cur)
+        frames[name] = cur.withColumn("lr_class", integer_codes(df, label_col))
+    model = LogisticRegression(featuresCol="features", labelCol="lr_class", family="multinomial",
+                               regParam=reg_param).fit(frames["Train"])
+    out = {"numClasses": model.numClasses}
+    for name, cur in frames.items():
+        pred = model.transform(cur).column("prediction")
+        pred = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
+        out[name] = {"Accuracy": float((pred == cur.column("lr_class")).mean()) if len(pred) else 0.0}
+        print(f"MultinomialLogisticRegression {name} accuracy: {out[name]['Accuracy']:.4f}")
+    return out
+
+
 def analyze_word_associations(spark, model: PipelineModel, df: Frame, vocab: list, top_n: int = 10) -> Optional[Frame]:
     """Top-N features by importance -> docs containing the word by label (full dataset, like the
     reference) -> [word, scam_count, non_scam_count, scam_ratio, importance] by importance desc."""
@@ -177,6 +210,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--no-plots", action="store_true")
     ap.add_argument("--ngram", type=int, default=1, help="insert an NGram(n) stage after the stop-word remover")
     ap.add_argument("--naive-bayes", action="store_true", help="also train Spark's multinomial NaiveBayes")
+    ap.add_argument("--lr-label-col", default=None, metavar="COL",
+                    help="also fit a multinomial LogisticRegression on the integer-coded column COL (classes 0 .. C - 1)")
     Config.add_cli_args(ap)          # --num-trees, --max-depth, --vocab-size, --seed, --device, --config ...
     args = ap.parse_args(argv)
     cfg = Config.from_cli(args)
@@ -228,6 +263,10 @@ def main(argv=None) -> dict:
                 if not args.no_plots:
                     plot_word_associations(ws, name, args.out_dir)
         summary = {n: {ds: v["metrics"] for ds, v in r.items()} for n, r in results.items()}
+        if args.lr_label_col:
+            summary["MultinomialLogisticRegression"] = fit_multinomial_lr(
+                next(iter(models.values())).stages[:-1], args.lr_label_col,
+                {"Train": train_df, "Validation": val_df, "Test": test_df})
         with open(os.path.join(args.out_dir, "results.json"), "w") as fh:
             json.dump({"metrics": summary, "word_stats": word_stats,
                        "split": [train_df.count(), val_df.count(), test_df.count()]}, fh, indent=2)
