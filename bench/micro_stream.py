@@ -1,6 +1,9 @@
 """Streaming-path breakdown on one GPU: pinned H2D bandwidth, kernel time, pipelined step time.
 
-Prints one JSON line per configuration so copy/compute overlap can be diagnosed.
+Prints one JSON line per configuration so copy/compute overlap can be diagnosed. ``--classes C``
+serves a C-class multinomial logistic-regression model (random coefficients) instead of the tree
+ensemble: the model's ``serving_scorer()`` in the scorer, its ``serving_postprocess`` in the
+``pipeline+post`` rows, and a ``csr_route`` row for the two-step way to the same class scores.
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--ngram", type=int, default=1, help="NGram width between the remover and HashingTF")
+    ap.add_argument("--classes", type=int, default=0, help="serve a C-class linear model instead of the trees")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     B = args.batch
@@ -35,6 +39,22 @@ def main():
 
     trees = random_forest_arrays(100, F, 6, 1, seed=1)
     idf = np.random.default_rng(0).random(F)
+    model = None
+    if args.classes:
+        from fraud_detection_spark_kafka_llm_amd.ml import LogisticRegressionModel
+
+        rng = np.random.default_rng(1)
+        model = LogisticRegressionModel(coefficientMatrix=rng.normal(size=(args.classes, F)),
+                                        interceptVector=rng.normal(size=args.classes))
+        trees = model.serving_scorer()      # the margin of a 2-class model, else its class scores
+
+    def post(raw):
+        if model is not None:
+            return model.serving_postprocess(raw)
+        return np.reciprocal(np.exp(-raw[:, 0]) + 1.0)
+
+    one = dict(zip(("lr", "trees", "classes"), (trees if isinstance(trees, k) else None for k in (
+        T.LinearScorer, T.TreeArrays, T.ClassLinearScorer))))
     ring = PinnedRing(slots=4, max_docs=B, max_bytes=B * 4096)
     for i, s in enumerate(ring.slots):
         pt, _ = synth.generate(synth.SynthConfig(n=B, seed=3), device=dev, start=i * B)
@@ -80,8 +100,7 @@ def main():
                 a = time.perf_counter()
                 _, raw = sc.collect(copy=False)
                 b = time.perf_counter()
-                m = raw[:, 0]
-                p = np.reciprocal(np.exp(-m) + 1.0)
+                post(raw)
                 c = time.perf_counter()
                 ts["collect_wait"] += b - a
                 ts["post"] += c - b
@@ -96,15 +115,38 @@ def main():
                           **{k + "_ms": v / args.steps * 1e3 for k, v in ts.items()}}), flush=True)
     # (c) kernel only (text resident)
     pt = T.PackedText(ring.slots[0].data[: nb + 16].to(dev), ring.slots[0].offsets[: B + 1].to(dev))
+    idf_t = torch.from_numpy(idf)
     for _ in range(3):
-        T.featurize_score(pt, spec, idf=torch.from_numpy(idf), trees=trees, device=dev, fix_fallbacks=False)
+        T.featurize_score(pt, spec, idf=idf_t, device=dev, fix_fallbacks=False, **one)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(20):
-        T.featurize_score(pt, spec, idf=torch.from_numpy(idf), trees=trees, device=dev, fix_fallbacks=False)
+        T.featurize_score(pt, spec, idf=idf_t, device=dev, fix_fallbacks=False, **one)
     torch.cuda.synchronize()
     k = (time.perf_counter() - t0) / 20
     print(json.dumps({"what": "kernel", "ms": k * 1e3, "docs_per_s": B / k}), flush=True)
+    if one["classes"] is not None:
+        # the two-step route to the same scores: want_csr launch, CSR compaction, nb_score
+        from fraud_detection_spark_kafka_llm_amd.ml.linalg import VectorColumn
+        from fraud_detection_spark_kafka_llm_amd.ops.sparse import score_csr
+
+        stored = T.ClassLinearScorer(one["classes"].W, one["classes"].b)      # scores the CSR's fp32 values
+
+        def csr_route():
+            res = T.featurize_score(pt, spec, idf=idf_t, want_csr=True, device=dev, fix_fallbacks=False)
+            return score_csr(VectorColumn(F, *res.csr()), stored)
+
+        single = T.featurize_score(pt, spec, idf=idf_t, device=dev, fix_fallbacks=False, classes=stored).raw
+        for _ in range(3):
+            two = csr_route()
+        assert torch.equal(two.view(torch.int64), single.view(torch.int64)), "single launch != CSR route"
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(20):
+            csr_route()
+        torch.cuda.synchronize()
+        k = (time.perf_counter() - t0) / 20
+        print(json.dumps({"what": "csr_route", "ms": k * 1e3, "docs_per_s": B / k}), flush=True)
 
 
 if __name__ == "__main__":

@@ -148,13 +148,30 @@ void featurize_score(const Tensor& text, const Tensor& doc_off, int64_t flags, i
                      const optional<std::vector<Tensor>>& trees, int64_t K, const Tensor& out_idx,
                      const Tensor& out_val, const Tensor& out_nnz, const optional<Tensor>& out_ntok,
                      const Tensor& out_raw, const Tensor& out_status, const optional<Tensor>& only_docs,
-                     int64_t threads, const optional<Tensor>& long_docs) {
+                     int64_t threads, const optional<Tensor>& long_docs, const optional<Tensor>& cls_w,
+                     const optional<Tensor>& cls_b) {
   const auto dev = text.device();
   check_dev(text, dev, "text");
   check_dev(doc_off, dev, "doc_off");
   FDX_CHECK(text.scalar_type() == at::kByte && doc_off.scalar_type() == at::kLong, "text u8 / doc_off i64");
   const int64_t D = doc_off.numel() - 1;
   FDX_CHECK(D >= 0, "doc_off needs at least one entry");
+  int64_t classes = 0;
+  if (flags & fdx::kFlagClasses) {      // C linear class scores: W [>= num_features, C] feature-major, b [C]
+    FDX_CHECK(!(flags & (fdx::kFlagLR | fdx::kFlagTrees)), "one scorer per launch (classes with lr or trees)");
+    FDX_CHECK(cls_w && cls_b && cls_w->defined() && cls_b->defined(), "class scores need W and b");
+    check_dev(*cls_w, dev, "class W");
+    check_dev(*cls_b, dev, "class b");
+    FDX_CHECK(cls_w->scalar_type() == at::kDouble && cls_b->scalar_type() == at::kDouble, "class W / b must be float64");
+    FDX_CHECK(cls_w->dim() == 2, "class W is [features, classes]");
+    classes = cls_w->size(1);
+    FDX_CHECK(classes >= 2 && classes <= fdx::kMaxClasses, "class scores take 2 .. 8 classes");
+    FDX_CHECK(cls_b->numel() == classes, "class b needs one entry per class");
+    FDX_CHECK(cls_w->size(0) >= num_features, "class W has fewer rows than the feature space");
+  } else {
+    FDX_CHECK(!(flags & fdx::kFlagClassExact), "exact class values without the class-score flag");
+    FDX_CHECK(!cls_w && !cls_b, "class W / b given without the class-score flag");
+  }
   for (const Tensor* t : {&out_idx, &out_val, &out_nnz}) check_dev(*t, dev, "outputs");
   FDX_CHECK(out_nnz.numel() >= D && out_status.numel() >= D, "per-doc outputs too small");
   FDX_CHECK(out_idx.numel() >= fdx::csr_capacity(text.numel(), D) || !(flags & fdx::kFlagWriteCsr),
@@ -164,7 +181,7 @@ void featurize_score(const Tensor& text, const Tensor& doc_off, int64_t flags, i
   if (flags & fdx::kFlagIdf) FDX_CHECK(idf && idf->numel() >= num_features && idf->scalar_type() == at::kDouble, "idf");
   if (flags & fdx::kFlagLR) FDX_CHECK(lr_w && lr_w->numel() >= num_features && lr_w->scalar_type() == at::kDouble, "lr_w");
   if (flags & fdx::kFlagTrees) FDX_CHECK(trees && K >= 1 && K <= 2, "trees");
-  FDX_CHECK(out_raw.numel() >= D * ((flags & fdx::kFlagTrees) ? K : 1), "out_raw too small");
+  FDX_CHECK(out_raw.numel() >= D * (classes ? classes : ((flags & fdx::kFlagTrees) ? K : 1)), "out_raw too small");
   if (idf) check_dev(*idf, dev, "idf");
   if (lr_w) check_dev(*lr_w, dev, "lr_w");
   if (out_ntok) check_dev(*out_ntok, dev, "out_ntok");
@@ -189,6 +206,9 @@ void featurize_score(const Tensor& text, const Tensor& doc_off, int64_t flags, i
   FDX_CHECK(out_raw.scalar_type() == at::kDouble && out_status.scalar_type() == at::kInt, "out_raw f64 / status i32");
   a.out_raw = out_ptr<double>(out_raw, dev, "out_raw");
   a.out_status = out_ptr<int32_t>(out_status, dev, "out_status");
+  a.cls_w = classes ? cls_w->data_ptr<double>() : nullptr;
+  a.cls_b = classes ? cls_b->data_ptr<double>() : nullptr;
+  a.num_classes = (int32_t)classes;
   if (dev.is_cuda()) {
     FDX_CHECK(!only_docs, "only_docs is a host-path option");
     if (long_docs) {      // second launch: the long-dialogue kernel on the listed documents only
@@ -717,7 +737,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_nb_ops(m);
   register_mlr_ops(m);
   m.def("token_keys", &token_keys, "CountVectorizer fit: 64-bit token keys (count pass / key pass)");
-  m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score");
+  m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score",
+        py::arg("text"), py::arg("doc_off"), py::arg("flags"), py::arg("num_features"), py::arg("stop"),
+        py::arg("vocab"), py::arg("min_tf"), py::arg("idf"), py::arg("lr_w"), py::arg("lr_b"), py::arg("trees"),
+        py::arg("K"), py::arg("out_idx"), py::arg("out_val"), py::arg("out_nnz"), py::arg("out_ntok"),
+        py::arg("out_raw"), py::arg("out_status"), py::arg("only_docs"), py::arg("threads"), py::arg("long_docs"),
+        py::arg("cls_w") = py::none(), py::arg("cls_b") = py::none());
   m.def("score_csr", &score_csr, "LR / tree-ensemble scoring of a CSR feature matrix");
   m.def("tree_contributions", &tree_contributions, "path-dependent TreeSHAP of one row tile over a path table");
   m.def("contrib_limits", &contrib_limits, "structural constants of the TreeSHAP kernels");

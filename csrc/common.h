@@ -110,7 +110,12 @@ enum : int {
   kFlagCmpLess = 1 << 8,      // tree split: go left iff x < thr (XGBoost); else x <= thr (Spark)
   kFlagPreLowered = 1 << 9,   // text already Unicode-lowercased by the host: pass UTF-8 through
   kFlagKeys = 1 << 10,        // CountVectorizer fit: emit a 64-bit key per kept token (no vectors)
+  kFlagClasses = 1 << 11,     // C linear class scores (FeatArgs::cls_w / cls_b), 2 <= C <= kMaxClasses
+  kFlagClassExact = 1 << 12,  // class scores multiply the fp64 value itself, not the fp32 the CSR stores
 };
+
+// Most classes of a linear class scorer: the fused featurizer's class tail and nb_score share it.
+constexpr int kMaxClasses = 8;
 
 // NGram stage (Spark ml.feature.NGram) between stop-word removal and the TF stage: bits 16-18 of
 // the flags word hold n - 1, so a unigram pipeline's word is what it was before the field existed.

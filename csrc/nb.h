@@ -22,7 +22,7 @@ namespace fdx {
 constexpr int kNbWave = 64;
 constexpr int kNbBlock = 256;                      // lanes of a workgroup of nb_sums / nb_score
 constexpr int kNbWaves = kNbBlock / kNbWave;
-constexpr int kNbMaxClasses = 8;
+constexpr int kNbMaxClasses = kMaxClasses;
 constexpr int kNbChunkRows = 1024;                 // default rows of a workgroup of nb_sums
 constexpr int64_t kNbMaxChunkRows = 1 << 20;
 constexpr int kNbTableBytes = 32 * 1024;           // default LDS table of the hot features [C][H] int64 (swept)

@@ -142,7 +142,7 @@ struct FeatArgs {
   float* out_val;
   int32_t* out_nnz;          // [num_docs]
   int32_t* out_ntok;         // [num_docs] tokens after stop-word removal, n-grams of them with NGram (may be null)
-  double* out_raw;           // [num_docs * K] (K = trees.K, or 1 for LR)
+  double* out_raw;           // [num_docs * K] (K = trees.K, num_classes with kFlagClasses, or 1 for LR)
   int32_t* out_status;       // [num_docs]
   // kFlagKeys: key of token i of doc d at out_keys[key_off[d] + i]; out_keys == nullptr -> count only
   const int64_t* key_off;
@@ -150,6 +150,12 @@ struct FeatArgs {
   // long-dialogue launch: process only doc_list[0 .. n_list) (nullptr: every document)
   const int32_t* doc_list;
   int32_t n_list;
+  // kFlagClasses: raw[d, c] = sum_j x_j * cls_w[u_j, c] (+ cls_b[c]) in nb_score's order, x_j = (double)(float)v_j:
+  // nb_score over the row kFlagWriteCsr would store. With kFlagClassExact x_j = v_j: nb_score over the fp64
+  // feature column of the staged pipeline. out_raw is [num_docs, num_classes] then
+  const double* cls_w;       // [>= num_features, num_classes] feature-major
+  const double* cls_b;       // [num_classes]
+  int32_t num_classes;       // 2 .. kMaxClasses
 };
 
 }  // namespace fdx

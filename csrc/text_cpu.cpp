@@ -147,6 +147,22 @@ void process_doc(const FeatArgs& a, int32_t d, std::string& clean, std::vector<u
     lr = part[0];
     a.out_raw[d] = lr + a.lr_b;
   }
+  if (a.flags & kFlagClasses) {
+    // The kernel's class tail: nb_score's order over the values as the CSR stores them (fp32), or over
+    // the fp64 values themselves with kFlagClassExact.
+    const int C = a.num_classes;
+    const bool exact = (a.flags & kFlagClassExact) != 0;
+    double part[64][kMaxClasses] = {};
+    for (int32_t j = 0; j < nu; ++j) {
+      const double x = exact ? vals[j] : (double)(float)vals[j];
+      const double* w = a.cls_w + (int64_t)runs[j].first * C;
+      for (int c = 0; c < C; ++c) part[j & 63][c] += x * w[c];
+    }
+    for (int o = 32; o > 0; o >>= 1)
+      for (int l = 0; l < 64; ++l) if (l < (l ^ o))
+        for (int c = 0; c < C; ++c) { const double t = part[l][c] + part[l ^ o][c]; part[l][c] = t; part[l ^ o][c] = t; }
+    for (int c = 0; c < C; ++c) a.out_raw[(int64_t)d * C + c] = part[0][c] + a.cls_b[c];
+  }
   if (a.flags & kFlagTrees) {
     const TreeEnsemble& te = a.trees;
     const bool cmp_less = (a.flags & kFlagCmpLess) != 0;

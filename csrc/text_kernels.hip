@@ -23,6 +23,11 @@
 // table, and a pass 4b gives lane i the n-gram that starts at kept token i, hashes its members'
 // bytes joined by ' ' and writes the bucket back into the table in place. From the sort onwards
 // the two modes are the same code; the unigram instantiations compile as if the mode did not exist.
+// With kFlagClasses a third set runs, one per class count C = 2 .. kMaxClasses: step 7 is then the C
+// linear class scores of a ClassLinearScorer in nb_score_kernel's order (a lane keeps C partials in
+// registers, one 8 C-byte gather of W[u][0 .. C) per term), and the LR / tree tails are compiled out.
+#include <stdexcept>
+
 #include "scoring.h"
 #include "ops.h"
 
@@ -83,8 +88,12 @@ __device__ __forceinline__ uint32_t hash_token(const uint8_t* s_clean, int p, in
   return m.finish();
 }
 
-template <int CAPB, int CAPT, int WAVES, bool NGRAM>
+// CLS > 0: the class-score instantiations (kFlagClasses with CLS classes). Their tail keeps a
+// lane's CLS partials in registers and replaces the LR / tree tails (one scorer per launch);
+// CLS == 0 compiles as if the mode did not exist.
+template <int CAPB, int CAPT, int WAVES, bool NGRAM, int CLS>
 __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs a) {
+  static_assert(CLS == 0 || (CLS >= 2 && CLS <= kMaxClasses), "class scores: 2 .. kMaxClasses");
   static_assert(CAPB / 4 >= CAPT && CAPB <= 65536, "counts reuse the byte buffer; token starts are 16-bit");
   __shared__ __attribute__((aligned(16))) uint8_t s_clean_all[WAVES][CAPB];
   __shared__ uint32_t s_tok_all[WAVES][CAPT];
@@ -364,6 +373,11 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
   const bool use_idf = (a.flags & kFlagIdf) != 0;
   const int64_t ob = csr_slot(s, d);   // CSR scratch base (scoring.h)
   double lr_part = 0.0;
+  double cls_part[CLS > 0 ? CLS : 1];
+  if constexpr (CLS > 0) {
+#pragma unroll
+    for (int c = 0; c < CLS; ++c) cls_part[c] = 0.0;
+  }
   for (int j = lane; j < nu; j += kWave) {
     const uint32_t u = s_tok[j];
     double v = binary ? 1.0 : (double)s_cnt[j];
@@ -372,12 +386,30 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
       a.out_idx[ob + j] = (int32_t)u;
       a.out_val[ob + j] = (float)v;
     }
-    if (a.flags & kFlagLR) lr_part += v * a.lr_w[u];
+    if constexpr (CLS > 0) {
+      // nb_score_kernel's term over the value the CSR stores (or the fp64 value itself): one gather of
+      // W[u][0 .. CLS)
+      const double x = (a.flags & kFlagClassExact) ? v : (double)(float)v;
+      const double* w = a.cls_w + (int64_t)u * CLS;
+#pragma unroll
+      for (int c = 0; c < CLS; ++c) cls_part[c] += x * w[c];
+    } else {
+      if (a.flags & kFlagLR) lr_part += v * a.lr_w[u];
+    }
   }
   if (lane == 0) {
     a.out_nnz[d] = nu;
     if (a.out_ntok) a.out_ntok[d] = nall;
     a.out_status[d] = kStatusOk;
+  }
+  if constexpr (CLS > 0) {
+#pragma unroll
+    for (int c = 0; c < CLS; ++c) cls_part[c] = wave_sum_f64(cls_part[c]);
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < CLS; ++c) a.out_raw[(int64_t)d * CLS + c] = cls_part[c] + a.cls_b[c];
+    }
+    return;
   }
   if (a.flags & kFlagLR) {
     const double m = wave_sum_f64(lr_part);
@@ -409,22 +441,39 @@ __global__ __launch_bounds__(kWave * WAVES) void featurize_score_kernel(FeatArgs
   }
 }
 
-template <bool NGRAM>
+template <bool NGRAM, int CLS>
 static void launch_mode(const FeatArgs& a, hipStream_t stream) {
   if (a.doc_list) {          // long dialogues: one per single-wave workgroup
     if (a.n_list > 0)
-      hipLaunchKernelGGL((featurize_score_kernel<kLongCapB, kLongCapT, 1, NGRAM>), dim3(a.n_list), dim3(kWave), 0,
-                         stream, a);
+      hipLaunchKernelGGL((featurize_score_kernel<kLongCapB, kLongCapT, 1, NGRAM, CLS>), dim3(a.n_list), dim3(kWave),
+                         0, stream, a);
     return;
   }
   if (a.num_docs <= 0) return;
   const int blocks = (a.num_docs + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL((featurize_score_kernel<kCapB, kCapT, kWavesPerBlock, NGRAM>), dim3(blocks),
+  hipLaunchKernelGGL((featurize_score_kernel<kCapB, kCapT, kWavesPerBlock, NGRAM, CLS>), dim3(blocks),
                      dim3(kWave * kWavesPerBlock), 0, stream, a);
 }
 
+template <int CLS>
+static void launch_classes(const FeatArgs& a, hipStream_t stream) {
+  if (ngram_of(a.flags) > 1) launch_mode<true, CLS>(a, stream); else launch_mode<false, CLS>(a, stream);
+}
+
 void launch_featurize_score(const FeatArgs& a, hipStream_t stream) {
-  if (ngram_of(a.flags) > 1) launch_mode<true>(a, stream); else launch_mode<false>(a, stream);
+  if (!(a.flags & kFlagClasses)) return launch_classes<0>(a, stream);
+  if ((a.flags & (kFlagLR | kFlagTrees | kFlagKeys)) || !a.cls_w || !a.cls_b)
+    throw std::runtime_error("fdx featurize_score: class scores take W and b and no other scorer");
+  switch (a.num_classes) {     // one instantiation per C, as nb_score_kernel<V, C>
+    case 2: return launch_classes<2>(a, stream);
+    case 3: return launch_classes<3>(a, stream);
+    case 4: return launch_classes<4>(a, stream);
+    case 5: return launch_classes<5>(a, stream);
+    case 6: return launch_classes<6>(a, stream);
+    case 7: return launch_classes<7>(a, stream);
+    case 8: return launch_classes<8>(a, stream);
+    default: throw std::runtime_error("fdx featurize_score: classes out of range");
+  }
 }
 
 }  // namespace fdx

@@ -218,6 +218,24 @@ def build_ngram_selftest(sanitize: bool = True, out: Path | None = None) -> Path
     return out
 
 
+def build_cls_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/cls_selftest.cpp`` + the fused featurizer's host twin (``text_cpu.cpp``) as a
+    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
+    ``build_ngram_selftest`` (host code only, one translation unit): the class-score tail."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("cls_selftest_asan" if sanitize else "cls_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "cls_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "text_cpu.cpp"}"\n#include "{CSRC / "tests" / "cls_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def build_lr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     """``csrc/tests/lr_selftest.cpp`` + the elastic-net logistic-regression host twins (``lr_cpu.cpp``, and
     ``sparse_cpu.cpp`` for the SpMV the margins must equal) as a standalone executable under
@@ -314,7 +332,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the Naive Bayes host twins")
     ap.add_argument("--mlr-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the multinomial logistic-regression host twin")
+    ap.add_argument("--cls-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the class-score tail of the featurizer's host twin")
     args = ap.parse_args(argv)
+    if args.cls_selftest:
+        return subprocess.run([str(build_cls_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.mlr_selftest:
         return subprocess.run([str(build_mlr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.nb_selftest:

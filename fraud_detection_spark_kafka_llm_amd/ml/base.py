@@ -318,11 +318,13 @@ class PipelineModel(Model):
             frame = s.transform(frame)
         return frame
 
-    def compile(self, device=None):
-        """Fused serving kernel for text -> prediction (see ``ml.fused.FusedPipeline``)."""
+    def compile(self, device=None, multiclass: bool = False):
+        """Fused serving kernel for text -> prediction (see ``ml.fused.FusedPipeline``). A classifier
+        with more than two classes compiles only with ``multiclass=True`` (its class scores then run
+        in the same single launch)."""
         from . import fused
 
-        return fused.FusedPipeline.from_stages(self.stages, device=device)
+        return fused.FusedPipeline.from_stages(self.stages, device=device, multiclass=multiclass)
 
     def _save_metadata(self, path) -> None:
         sf.write_metadata(path, self._java_class, self.uid, {"stageUids": [s.uid for s in self.stages]}, {})

@@ -52,6 +52,24 @@ class ClassificationModelBase(_PredictorParams, Model):
         _, prob, pred = self.postprocess(torch.from_numpy(raw))
         return pred.numpy(), prob[:, 1].numpy()
 
+    def serving_scorer(self):
+        """The scorer of the serving paths (``FusedPipeline(multiclass=True)``, the agent, the
+        streaming engine): ``scorer()``, or the ``ClassLinearScorer`` of a model with more than two
+        classes (``scorer()`` itself keeps raising for those)."""
+        return self.scorer()
+
+    def serving_postprocess(self, raw: np.ndarray):
+        """Streaming hot path of ``serving_scorer()``'s output: raw [N, K] fp64 numpy -> (prediction [N],
+        confidence [N]). For the ``[N, numClasses]`` class scores of a model with more than two classes
+        ``prediction`` is ``postprocess``'s decision (the first argmax of the probability, or of
+        ``p_c / t_c`` under NaiveBayes ``thresholds``) and ``confidence`` the probability of the predicted
+        class; in every other case this is ``postprocess_numpy``: ``confidence = P(class 1)``."""
+        if self.numClasses > 2 and raw.ndim == 2 and raw.shape[1] == self.numClasses:
+            _, prob, pred = self.postprocess(torch.from_numpy(np.ascontiguousarray(raw)))
+            pred, prob = pred.numpy(), prob.numpy()
+            return pred, prob[np.arange(prob.shape[0]), pred.astype(np.int64)]
+        return self.postprocess_numpy(raw)
+
     def _transform(self, frame: Frame) -> Frame:
         from ..ops.sparse import score_csr
 
@@ -260,7 +278,7 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
         if not self.isMultinomial:
             raise ValueError("a binomial model scores one margin: use scorer()")
         if self._class_scorer is None:
-            self._class_scorer = ClassLinearScorer(np.ascontiguousarray(self._W.T), self._b)
+            self._class_scorer = ClassLinearScorer(np.ascontiguousarray(self._W.T), self._b, exact=True)
         return self._class_scorer
 
     def scorer(self) -> LinearScorer:
@@ -273,6 +291,9 @@ class LogisticRegressionModel(_LRParams, ClassificationModelBase):
             self._scorer = LinearScorer(self._W[1] - self._W[0], float(self._b[1] - self._b[0])) \
                 if self.isMultinomial else LinearScorer(self.coefficients, self.intercept)
         return self._scorer
+
+    def serving_scorer(self):
+        return self.class_scorer() if self.numClasses > 2 else self.scorer()
 
     def postprocess(self, raw: torch.Tensor):
         if self.isMultinomial:
@@ -639,7 +660,7 @@ class NaiveBayesModel(_NBParams, ClassificationModelBase):
         if self._class_scorer is None:
             from ..models.nb import class_linear
 
-            self._class_scorer = ClassLinearScorer(*class_linear(self.pi, self.theta, self.getModelType()))
+            self._class_scorer = ClassLinearScorer(*class_linear(self.pi, self.theta, self.getModelType()), exact=True)
         return self._class_scorer
 
     def scorer(self) -> LinearScorer:
@@ -651,6 +672,9 @@ class NaiveBayesModel(_NBParams, ClassificationModelBase):
             cs = self.class_scorer()
             self._scorer = LinearScorer(cs.W[:, 1] - cs.W[:, 0], float(cs.b[1] - cs.b[0]))
         return self._scorer
+
+    def serving_scorer(self):
+        return self.class_scorer() if self.numClasses > 2 else self.scorer()
 
     def _thresholds(self, like: torch.Tensor) -> Optional[torch.Tensor]:
         if not self.isSet("thresholds"):

@@ -21,10 +21,16 @@ from .linalg import VectorColumn
 
 
 class FusedPipeline:
-    """Compiled text->score chain. ``predict`` returns (prediction, probability, rawPrediction)."""
+    """Compiled text->score chain. ``predict`` returns (prediction, probability, rawPrediction).
+
+    ``multiclass=True`` takes the model's ``serving_scorer()``: a model with more than two classes
+    (NaiveBayes, multinomial logistic regression) then runs its ``C`` class scores in the same single
+    launch and ``predict`` returns ``[N, C]`` probabilities and raw predictions, bit for bit
+    ``transform``'s. Without it such a model raises, as its ``scorer()`` does."""
 
     def __init__(self, tokenizer: Tokenizer, remover: Optional[StopWordsRemover], tf, idf: Optional[IDFModel],
-                 model: Optional[ClassificationModelBase], ngram: Optional[NGram] = None, device=None):
+                 model: Optional[ClassificationModelBase], ngram: Optional[NGram] = None, device=None,
+                 multiclass: bool = False):
         self.tokenizer, self.remover, self.tf, self.idf, self.model = tokenizer, remover, tf, idf, model
         self.ngram = int(ngram.getN()) if ngram is not None else 1
         self.device = torch.device(device) if device is not None else default_device()
@@ -38,14 +44,17 @@ class FusedPipeline:
         if model is not None and model.numFeatures > self.dim:
             raise ValueError("classifier expects more features than the TF stage produces")
         self._idf_t = idf.idf_tensor(self.device) if idf is not None else None
-        self._scorer = model.scorer() if model is not None else None
+        self.multiclass = bool(multiclass)
+        self._scorer = None
+        if model is not None:
+            self._scorer = model.serving_scorer() if self.multiclass else model.scorer()
 
     @classmethod
-    def from_stages(cls, stages: Sequence, device=None) -> "FusedPipeline":
+    def from_stages(cls, stages: Sequence, device=None, multiclass: bool = False) -> "FusedPipeline":
         chain = match_chain(stages)
         if chain is None or chain[-1] != len(stages):
             raise ValueError("pipeline is not a fusable text->classifier chain")
-        return cls(*chain[:6], device=device)
+        return cls(*chain[:6], device=device, multiclass=multiclass)
 
     def spec(self, clean: bool) -> FeatureSpec:
         return self._spec_clean if clean else self._spec_raw
@@ -55,18 +64,19 @@ class FusedPipeline:
         (agent_api.py:139-145) inside the kernel."""
         dev = torch.device(device) if device is not None else self.device
         packed = texts if isinstance(texts, PackedText) else PackedText.from_strings(list(texts))
-        from .classification import LogisticRegressionModel
-        from ..ops.text import LinearScorer
+        from ..ops.text import ClassLinearScorer, LinearScorer
 
         lr = self._scorer if isinstance(self._scorer, LinearScorer) else None
-        trees = None if lr is not None or self._scorer is None else self._scorer
+        classes = self._scorer if isinstance(self._scorer, ClassLinearScorer) else None
+        trees = None if lr is not None or classes is not None or self._scorer is None else self._scorer
         if lr is not None and lr.w.size < self.dim:
             import numpy as np
 
             lr = LinearScorer(np.concatenate([lr.w, np.zeros(self.dim - lr.w.size)]), lr.b)
             self._scorer = lr
         idf = self.idf.idf_tensor(dev) if self.idf is not None else None
-        return featurize_score(packed, self.spec(clean), idf=idf, lr=lr, trees=trees, want_csr=want_csr, device=dev)
+        return featurize_score(packed, self.spec(clean), idf=idf, lr=lr, trees=trees, want_csr=want_csr, device=dev,
+                               classes=classes)
 
     def predict(self, texts, clean: bool = True, device=None):
         if self.model is None:
@@ -142,10 +152,15 @@ class _Plan:
                 return VectorColumn.scaled_counts(vc.size, ip, ix, v, w)
             frame = frame.withColumn(idf.getOutputCol(), Lazy(_idf, n))
         if isinstance(model, NaiveBayesModel) or (isinstance(model, LogisticRegressionModel) and model.isMultinomial):
-            # C class scores: the fused launch's CSR (the lazy feature column above: want_csr, no
-            # scorer) scored by score_csr's nb_score, so rawPrediction is Spark's and the outputs
-            # equal the staged transform bit for bit
-            frame = model.transform(frame)
+            # C class scores in the same single launch: the kernel's class tail is nb_score's sum over
+            # the fp64 values of the feature column (class_scorer() is exact), so rawPrediction is
+            # Spark's and the outputs equal the staged transform bit for bit; the feature columns stay lazy
+            fp = FusedPipeline(tok, rem, tf, idf, None, self.ngram)
+            if fp.dim < model.numFeatures:
+                raise ValueError(f"features have size {fp.dim}, model expects {model.numFeatures}")
+            fp._scorer = model.class_scorer()     # also of a 2-class model: transform gives Spark's [N, 2]
+            res = fp.run(raw.packed(), clean=clean)
+            frame = model.attach_outputs(frame, res.raw)
         elif model is not None:
             fp = FusedPipeline(tok, rem, tf, idf, model, self.ngram)
             res = fp.run(raw.packed(), clean=clean)

@@ -51,13 +51,15 @@ def split_points(buf: np.ndarray, s: int, e: int, seg: int = SEG_BYTES) -> Optio
 
 
 def featurize_long(data_dev: torch.Tensor, host_buf: np.ndarray, doc_off: np.ndarray, docs: np.ndarray, spec,
-                   idf_t: Optional[torch.Tensor], lr, trees, device):
+                   idf_t: Optional[torch.Tensor], lr, trees, device, classes=None):
     """Score dialogues ``docs`` (indices into ``doc_off``) whose bytes are ``data_dev`` (device)
     and ``host_buf`` (the same bytes on the host, for the cut search).
 
     Returns ``(done, raw, nnz, ntok, csr)``: ``done`` bool [len(docs)] (False: left to the host),
     ``raw`` [n_done, K] fp64 on ``device``, ``nnz``/``ntok`` int32 [n_done], and ``csr`` =
-    (indptr int64 [n_done+1], idx int32, val fp64) of the merged rows."""
+    (indptr int64 [n_done+1], idx int32, val fp64) of the merged rows. With ``classes`` (a
+    ``ClassLinearScorer``) ``raw`` is the ``C`` class scores of the merged rows' values, rounded to
+    fp32 unless ``classes.exact``: the fused kernel's class-score contract."""
     from . import native
     from .sparse import score_csr
     from ..ml.linalg import VectorColumn
@@ -72,7 +74,7 @@ def featurize_long(data_dev: torch.Tensor, host_buf: np.ndarray, doc_off: np.nda
         done[j] = True
         bounds.append(b)
         seg_doc.append(np.full(b.size - 1, j, dtype=np.int64))
-    K = trees.K if trees is not None else 1
+    K = trees.K if trees is not None else (classes.num_classes if classes is not None else 1)
     empty = (done, torch.zeros((0, K), dtype=torch.float64, device=device), torch.zeros(0, dtype=torch.int32),
              torch.zeros(0, dtype=torch.int32), None)
     if not bounds:
@@ -137,6 +139,9 @@ def featurize_long(data_dev: torch.Tensor, host_buf: np.ndarray, doc_off: np.nda
     per = torch.bincount(row, minlength=n_done)
     indptr = torch.zeros(n_done + 1, dtype=torch.int64, device=device)
     torch.cumsum(per, 0, out=indptr[1:])
+    if classes is not None:     # the class tail scores the values as the CSR scratch stores them, or exactly
+        raw = score_csr(VectorColumn(int(spec.dim), indptr, col, v if classes.exact else v.to(torch.float32)), classes)
+        return done, raw, per.to(torch.int32), tok.to(torch.int32), (indptr, col, v)
     vc = VectorColumn(int(spec.dim), indptr, col, v)
     scorer = lr if lr is not None else trees
     raw = score_csr(vc, scorer) if scorer is not None else torch.zeros((n_done, 1), dtype=torch.float64, device=device)

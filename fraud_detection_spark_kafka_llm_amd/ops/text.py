@@ -32,6 +32,9 @@ FLAG_VOCAB = 1 << 6
 FLAG_STOPWORDS = 1 << 7
 FLAG_CMP_LESS = 1 << 8
 FLAG_PRELOWERED = 1 << 9
+FLAG_CLASSES = 1 << 11   # C linear class scores (ClassLinearScorer) instead of the LR margin / tree sums
+FLAG_CLASS_EXACT = 1 << 12   # ... of the fp64 values themselves, not of the fp32 values the CSR stores
+MAX_CLASSES = 8          # csrc/common.h kMaxClasses
 NGRAM_SHIFT = 16         # bits 16-18 of the flags word: NGram width - 1 (0 for a unigram pipeline)
 NGRAM_MAX = 8            # widest n-gram the fused kernel takes; wider ones run on the host stages
 STATUS_OK, STATUS_TOO_LONG, STATUS_NEEDS_HOST = 0, 1, 2
@@ -209,9 +212,16 @@ class LinearScorer(_DeviceCached):
 
 class ClassLinearScorer(_DeviceCached):
     """``C`` linear class scores ``x . W[:, c] + b[c]`` (fp64): ``W`` feature-major ``[F, C]``, so
-    one gather brings every class of an entry (``csrc/nb_kernels.hip::nb_score_kernel``)."""
+    one gather brings every class of an entry (``csrc/nb_kernels.hip::nb_score_kernel``).
 
-    def __init__(self, W: np.ndarray, b: np.ndarray):
+    ``exact`` only matters to the fused featurize+score launch, which makes its own values: by default
+    it multiplies the value as the CSR scratch stores it (rounded to fp32), so its class scores are
+    bitwise ``score_csr`` of the launch's own CSR; with ``exact=True`` it multiplies the fp64 value
+    itself (count or 1, times IDF), so they are bitwise ``score_csr`` of the staged pipeline's fp64
+    feature column: what ``transform`` gives. The models' ``class_scorer()`` are of that kind."""
+
+    def __init__(self, W: np.ndarray, b: np.ndarray, exact: bool = False):
+        self.exact = bool(exact)
         self.W = np.ascontiguousarray(W, dtype=np.float64)
         self.b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
         if self.W.ndim != 2 or self.W.shape[1] != self.b.size:
@@ -225,7 +235,12 @@ class ClassLinearScorer(_DeviceCached):
         """(W, b) on ``device``; ``size`` > F pads W with rows of zeros (features the model lacks)."""
         W, b = self._cached(device, lambda d: (torch.from_numpy(self.W).to(d), torch.from_numpy(self.b).to(d)))
         if size is not None and size > W.shape[0]:
-            W = torch.cat([W, torch.zeros((size - W.shape[0], W.shape[1]), dtype=torch.float64, device=W.device)])
+            padded = self.__dict__.setdefault("_padcache", {})
+            key = (str(W.device), int(size))
+            if key not in padded:
+                padded[key] = torch.cat([W, torch.zeros((size - W.shape[0], W.shape[1]), dtype=torch.float64,
+                                                        device=W.device)])
+            W = padded[key]
         return W, b
 
 
@@ -328,7 +343,8 @@ class TreePaths(_DeviceCached):
 
 # ----------------------------------------------------------------------------- results
 class FeatureResult:
-    """Outputs of one fused launch. ``raw`` is ``[D, K]`` fp64 (LR: margin; trees: raw sums)."""
+    """Outputs of one fused launch. ``raw`` is ``[D, K]`` fp64 (LR: margin; trees: raw sums; a
+    ``ClassLinearScorer``: its ``C`` class scores)."""
 
     def __init__(self, nnz, ntok, raw, status, idx, val, base, dim):
         self.nnz, self.ntok, self.raw, self.status = nnz, ntok, raw, status
@@ -370,8 +386,10 @@ class FeatureResult:
         return self.idx[pos], self.val[pos]
 
 
-def _flags(spec: FeatureSpec, idf, lr, trees, want_csr: bool) -> int:
+def _flags(spec: FeatureSpec, idf, lr, trees, want_csr: bool, classes=None) -> int:
     f = 0
+    if classes is not None:
+        f = FLAG_CLASSES | (FLAG_CLASS_EXACT if classes.exact else 0)
     if spec.clean:
         f |= FLAG_CLEAN
     if spec.binary:
@@ -411,27 +429,44 @@ def csr_slots(starts: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
 LONG_DOC_BYTES = 65536   # documents up to this size stay on the GPU (long-dialogue kernel)
 
 
-def _launch(C, text: PackedText, spec, flags, idf_t, lr, trees, out, device, only=None, threads=0, long_docs=None):
+def _check_scorers(spec: FeatureSpec, lr, trees, classes) -> None:
+    """One scorer per launch; a class scorer has 2 .. MAX_CLASSES classes and fits the feature space."""
+    if sum(s is not None for s in (lr, trees, classes)) > 1:
+        raise ValueError("one scorer per launch")
+    if classes is not None:
+        if not isinstance(classes, ClassLinearScorer):
+            raise TypeError("classes must be a ClassLinearScorer")
+        if not 2 <= classes.num_classes <= MAX_CLASSES:
+            raise ValueError(f"class scores take 2 to {MAX_CLASSES} classes, got {classes.num_classes}")
+        if classes.W.shape[0] > spec.dim:
+            raise ValueError("coefficient matrix longer than the feature space")
+
+
+def _launch(C, text: PackedText, spec, flags, idf_t, lr, trees, out, device, only=None, threads=0, long_docs=None,
+            classes=None):
     nnz, ntok, raw, status, idx, val = out
     st = spec.stop_table()
     vt = spec.vocab_table()
     K = trees.K if trees is not None else 1
+    # W padded with rows of zeros up to the feature space: a term id never indexes past it
+    cls = classes.tensors(device, spec.dim) if classes is not None else (None, None)
     C.featurize_score(
         text.data, text.offsets, flags, spec.dim,
         st.tensors(device) if st else None, vt.tensors(device) if vt else None,
         float(spec.min_tf), idf_t, lr.weights(device) if lr is not None else None,
         float(lr.b) if lr is not None else 0.0,
         trees.tensors(device) if trees is not None else None, K,
-        idx, val, nnz, ntok, raw, status, only, int(threads), long_docs)
+        idx, val, nnz, ntok, raw, status, only, int(threads), long_docs, *cls)
 
 
 def featurize_score(text: PackedText, spec: FeatureSpec, idf: Optional[torch.Tensor] = None,
                     lr: Optional[LinearScorer] = None, trees: Optional[TreeArrays] = None,
                     want_csr: bool = False, device=None, threads: int = 0,
-                    fix_fallbacks: bool = True) -> FeatureResult:
-    """Run the fused pipeline over ``text`` on ``device`` (default: where ``text`` lives)."""
-    if lr is not None and trees is not None:
-        raise ValueError("one scorer per launch")
+                    fix_fallbacks: bool = True, classes: Optional[ClassLinearScorer] = None) -> FeatureResult:
+    """Run the fused pipeline over ``text`` on ``device`` (default: where ``text`` lives). ``classes``
+    makes ``raw`` the ``[D, C]`` class scores: bitwise ``score_csr`` of the launch's own CSR, or of the
+    staged pipeline's fp64 feature column when the scorer is ``exact`` (see ``ClassLinearScorer``)."""
+    _check_scorers(spec, lr, trees, classes)
     C = native.lib()
     device = torch.device(device) if device is not None else text.device
     host_text = text
@@ -444,14 +479,14 @@ def featurize_score(text: PackedText, spec: FeatureSpec, idf: Optional[torch.Ten
         idf_t = idf.to(device=device, dtype=torch.float64)
         if idf_t.numel() < spec.dim:
             raise ValueError("idf vector shorter than the feature space")
-    K = trees.K if trees is not None else 1
+    K = trees.K if trees is not None else (classes.num_classes if classes is not None else 1)
     cap = csr_capacity(text.data.numel(), D) if want_csr else 1
     i32 = dict(dtype=torch.int32, device=device)
     out = (torch.zeros(D, **i32), torch.zeros(D, **i32),
            torch.zeros((D, K), dtype=torch.float64, device=device), torch.full((D,), -1, **i32),
            torch.empty(cap, **i32), torch.empty(cap, dtype=torch.float32, device=device))
-    flags = _flags(spec, idf_t, lr, trees, want_csr)
-    _launch(C, text, spec, flags, idf_t, lr, trees, out, device, None, threads)
+    flags = _flags(spec, idf_t, lr, trees, want_csr, classes)
+    _launch(C, text, spec, flags, idf_t, lr, trees, out, device, None, threads, classes=classes)
     nnz, ntok, raw, status, idx, val = out
     if device.type == "cuda" and D:
         # documents over the streaming kernel's LDS capacity: rerun them on the long-dialogue kernel
@@ -459,20 +494,20 @@ def featurize_score(text: PackedText, spec: FeatureSpec, idf: Optional[torch.Ten
         long_docs = torch.nonzero((status == STATUS_TOO_LONG) & (lens <= LONG_DOC_BYTES)).flatten()
         if long_docs.numel():
             _launch(C, text, spec, flags, idf_t, lr, trees, out, device, None, threads,
-                    long_docs.to(torch.int32).contiguous())
+                    long_docs.to(torch.int32).contiguous(), classes=classes)
     base = csr_slots(text.offsets[:-1], torch.arange(D, device=device, dtype=torch.int64))
     res = FeatureResult(nnz, ntok, raw, status, idx if want_csr else None, val if want_csr else None, base, spec.dim)
     if device.type == "cuda" and D:
-        _long_docs_on_device(res, text, host_text, spec, idf_t, lr, trees, want_csr, device)
+        _long_docs_on_device(res, text, host_text, spec, idf_t, lr, trees, want_csr, device, classes)
     if fix_fallbacks and D:
         bad = torch.nonzero(status != STATUS_OK).flatten()
         if bad.numel():
-            _finish_on_host(res, host_text, bad.cpu().numpy(), spec, idf, lr, trees, want_csr, flags)
+            _finish_on_host(res, host_text, bad.cpu().numpy(), spec, idf, lr, trees, want_csr, flags, classes)
     return res
 
 
 def _long_docs_on_device(res: FeatureResult, text: PackedText, host_text: PackedText, spec, idf_t, lr, trees,
-                         want_csr: bool, device) -> None:
+                         want_csr: bool, device, classes=None) -> None:
     """Dialogues over LONG_DOC_BYTES: segmented device path (ops/longdoc.py), patched into ``res``."""
     from .longdoc import featurize_long
 
@@ -483,7 +518,7 @@ def _long_docs_on_device(res: FeatureResult, text: PackedText, host_text: Packed
     docs = very.cpu().numpy()
     host_buf = host_text.data.cpu().numpy() if host_text.data.is_cuda else host_text.data.numpy()
     done, raw, nnz, ntok, csr = featurize_long(text.data, host_buf, text.offsets.cpu().numpy(), docs, spec, idf_t,
-                                               lr, trees, device)
+                                               lr, trees, device, classes)
     if not done.any():
         return
     d = torch.from_numpy(docs[done].astype(np.int64)).to(device)
@@ -502,7 +537,7 @@ def _long_docs_on_device(res: FeatureResult, text: PackedText, host_text: Packed
 
 
 def _finish_on_host(res: FeatureResult, text: PackedText, bad: np.ndarray, spec, idf, lr, trees,
-                    want_csr: bool, flags: int) -> None:
+                    want_csr: bool, flags: int, classes=None) -> None:
     """Re-run flagged documents on the host path and patch them into ``res``."""
     strings = text.strings()
     sub_strings = []
@@ -514,13 +549,13 @@ def _finish_on_host(res: FeatureResult, text: PackedText, bad: np.ndarray, spec,
     sub = PackedText.from_strings(sub_strings)
     sub_flags = flags | (0 if spec.clean else FLAG_PRELOWERED)
     D = len(sub)
-    K = trees.K if trees is not None else 1
+    K = trees.K if trees is not None else (classes.num_classes if classes is not None else 1)
     cap = csr_capacity(sub.data.numel(), D) if want_csr else 1
     i32 = dict(dtype=torch.int32)
     out = (torch.zeros(D, **i32), torch.zeros(D, **i32), torch.zeros((D, K), dtype=torch.float64),
            torch.full((D,), -1, **i32), torch.empty(cap, **i32), torch.empty(cap, dtype=torch.float32))
     idf_c = idf.to("cpu", torch.float64) if idf is not None else None
-    _launch(native.lib(), sub, spec, sub_flags, idf_c, lr, trees, out, torch.device("cpu"))
+    _launch(native.lib(), sub, spec, sub_flags, idf_c, lr, trees, out, torch.device("cpu"), classes=classes)
     nnz, ntok, raw, status, idx, val = out
     if torch.any(status != STATUS_OK):
         raise RuntimeError("host featurizer failed on fallback documents")

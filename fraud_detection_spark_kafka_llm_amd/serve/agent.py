@@ -12,7 +12,9 @@ Same public surface as the reference's ``DeepSeekClassificationAgent``
 * ``find_similar_historical_cases`` ranks historical dialogues by cosine similarity of their
   TF-IDF vectors (the reference returns the first ``n`` rows as a placeholder).
 
-``confidence`` keeps the reference's meaning: P(class 1 = fraud), whatever the prediction.
+``confidence`` keeps the reference's meaning: P(class 1 = fraud), whatever the prediction. A
+pipeline with more than two classes (NaiveBayes, multinomial logistic regression; the reference has
+none) reports the probability of the predicted class instead.
 """
 from __future__ import annotations
 
@@ -37,7 +39,7 @@ class ClassificationAgent:
                  analyzer: Optional[Analyzer] = None):
         self.device = torch.device(device) if device is not None else default_device()
         self.model = PipelineModel.load(model_path)
-        self.fused: FusedPipeline = self.model.compile(self.device)
+        self.fused: FusedPipeline = self.model.compile(self.device, multiclass=True)
         self.analyzer = analyzer or Analyzer(llm if llm is not None else make_llm())
         self._historical: Optional[Frame] = None
         self._hist_index = None
@@ -66,7 +68,15 @@ class ClassificationAgent:
     def predict_batch(self, texts: Sequence[str]) -> list:
         if not len(texts):
             return []
-        pred, prob, _ = self.fused.predict([t if t is not None else "" for t in texts], clean=True)
+        texts = [t if t is not None else "" for t in texts]
+        model = self.fused.model
+        if model is not None and model.numClasses > 2:
+            # class scores: the decision of the model's postprocess and the probability of the predicted
+            # class, computed as the streaming engine computes them (serving_postprocess)
+            raw = self.fused.run(texts, clean=True).raw.cpu().numpy()
+            pred, conf = model.serving_postprocess(raw)
+            return [{"prediction": float(a), "confidence": float(b)} for a, b in zip(pred, conf)]
+        pred, prob, _ = self.fused.predict(texts, clean=True)
         pred = pred.cpu().numpy()
         p1 = prob[:, 1].cpu().numpy()
         return [{"prediction": float(a), "confidence": float(b)} for a, b in zip(pred, p1)]

@@ -501,9 +501,11 @@ class StreamingEngine:
         fp = agent.fused
         idf = fp.idf.idf if fp.idf is not None else None
         devs = list(devices) if devices else [device or agent.device]
-        scorer = make_multi_scorer(fp.spec(True), idf, fp.model.scorer(), devs,
+        # serving_scorer / serving_postprocess: the margin and P(class 1) of a binary model, the class
+        # scores and the predicted class's probability of a model with more than two classes
+        scorer = make_multi_scorer(fp.spec(True), idf, fp.model.serving_scorer(), devs,
                                    max_docs=kw.get("batch_max", 4096), max_bytes=kw.get("max_bytes", 64 << 20))
-        return cls(scorer, fp.model.postprocess_numpy, consumer, producer, output_topic, agent=agent, **kw)
+        return cls(scorer, fp.model.serving_postprocess, consumer, producer, output_topic, agent=agent, **kw)
 
     def stop(self) -> None:
         self._stop.set()

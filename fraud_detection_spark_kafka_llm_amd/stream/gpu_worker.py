@@ -18,12 +18,25 @@ import numpy as np
 import torch
 
 from ..ops import native
-from ..ops.text import (FLAG_IDF, FLAG_LR, FLAG_TREES, LONG_DOC_BYTES, PAD, STATUS_OK, FeatureSpec, LinearScorer,
-                        PackedText, TreeArrays, _flags, featurize_score)
+from ..ops.text import (FLAG_IDF, FLAG_LR, FLAG_TREES, LONG_DOC_BYTES, PAD, STATUS_OK, ClassLinearScorer, FeatureSpec,
+                        LinearScorer, PackedText, TreeArrays, _check_scorers, _flags, featurize_score)
 from .ring import Slot
 
 
 LONG_DOC_MIN = 4096      # raw bytes above which the streaming kernel defers to the long-dialogue kernel
+
+
+def _split_scorer(scorer) -> tuple:
+    """(lr, trees, classes): the scorer in the slot of its kind."""
+    return (scorer if isinstance(scorer, LinearScorer) else None, scorer if isinstance(scorer, TreeArrays) else None,
+            scorer if isinstance(scorer, ClassLinearScorer) else None)
+
+
+def _score_width(scorer) -> int:
+    """Scores per dialogue: the leaf width of a tree ensemble, the classes of a class scorer, else 1."""
+    if isinstance(scorer, TreeArrays):
+        return scorer.K
+    return scorer.num_classes if isinstance(scorer, ClassLinearScorer) else 1
 
 
 @dataclass
@@ -49,16 +62,18 @@ class _Stage:
 class GpuScorer:
     def __init__(self, spec: FeatureSpec, idf: Optional[np.ndarray], scorer, device, max_docs: int = 65536,
                  max_bytes: int = 256 << 20, depth: int = 2):
-        if not isinstance(scorer, (LinearScorer, TreeArrays)):
-            raise TypeError("scorer must be LinearScorer or TreeArrays")
+        if not isinstance(scorer, (LinearScorer, TreeArrays, ClassLinearScorer)):
+            raise TypeError("scorer must be LinearScorer, TreeArrays or ClassLinearScorer")
         self.spec, self.scorer = spec, scorer
         self.dev = torch.device(device)
         self.C = native.lib()
-        self.K = scorer.K if isinstance(scorer, TreeArrays) else 1
+        self.K = _score_width(scorer)
         self.idf = torch.as_tensor(np.asarray(idf, dtype=np.float64)).to(self.dev) if idf is not None else None
-        lr = scorer if isinstance(scorer, LinearScorer) else None
-        trees = scorer if isinstance(scorer, TreeArrays) else None
-        self.flags = _flags(spec, self.idf, lr, trees, want_csr=False)
+        lr, trees, classes = _split_scorer(scorer)
+        _check_scorers(spec, lr, trees, classes)
+        self.flags = _flags(spec, self.idf, lr, trees, want_csr=False, classes=classes)
+        # class scores: W padded with rows of zeros up to the feature space, once
+        self.cls = classes.tensors(self.dev, spec.dim) if classes is not None else (None, None)
         self.stop = spec.stop_table().tensors(self.dev) if spec.stop_table() else None
         self.vocab = spec.vocab_table().tensors(self.dev) if spec.vocab_table() else None
         self.lr_w = lr.weights(self.dev) if lr is not None else None
@@ -128,16 +143,15 @@ class GpuScorer:
                         float(self.spec.min_tf), self.idf, self.lr_w,
                         float(self.scorer.b) if self.lr_w is not None else 0.0, self.tree_t, self.K, self.dummy_i,
                         self.dummy_f, st.nnz, st.ntok, st.h_raw, st.h_status, None, 0)
-                self.C.featurize_score(*args, None)
+                self.C.featurize_score(*args, None, *self.cls)
                 if long_idx is not None:      # dialogues over 4 KB: long-dialogue kernel, same stream
-                    self.C.featurize_score(*args, long_idx)
+                    self.C.featurize_score(*args, long_idx, *self.cls)
                 if very is not None and very.size:    # over 64 KB: segmented device path (rare; syncs)
                     from ..ops.longdoc import featurize_long
 
-                    lr = self.scorer if isinstance(self.scorer, LinearScorer) else None
-                    tr = self.scorer if isinstance(self.scorer, TreeArrays) else None
+                    lr, tr, classes = _split_scorer(self.scorer)
                     done, raw_l, *_ = featurize_long(st.text, slot.data.numpy(), offs, very, self.spec, self.idf, lr,
-                                                     tr, self.dev)
+                                                     tr, self.dev, classes)
                     st.very_long = (very[done], raw_l.cpu().numpy())
             st.ev_compute.record(self.compute)
             st.ev_d2h = st.ev_compute
@@ -165,10 +179,9 @@ class GpuScorer:
             bad = np.nonzero(status != STATUS_OK)[0]
             sub = PackedText.from_strings([bytes(st.slot.data[int(st.slot.offsets[i]):int(st.slot.offsets[i + 1])]
                                                  .numpy()).decode("utf-8", "replace") for i in bad])
-            lr = self.scorer if isinstance(self.scorer, LinearScorer) else None
-            tr = self.scorer if isinstance(self.scorer, TreeArrays) else None
+            lr, tr, classes = _split_scorer(self.scorer)
             fix = featurize_score(sub, self.spec, idf=self.idf.cpu() if self.idf is not None else None, lr=lr,
-                                  trees=tr, device="cpu")
+                                  trees=tr, device="cpu", classes=classes)
             raw = raw.copy()
             raw[bad] = fix.raw.numpy()
         slot = st.slot
@@ -209,9 +222,8 @@ class HostScorer:
             raise RuntimeError("pipeline full: call collect() first")
         n, nb = slot.n_docs, slot.n_bytes
         pt = PackedText(slot.data[: nb + PAD], slot.offsets[: n + 1].clone())
-        lr = self.scorer if isinstance(self.scorer, LinearScorer) else None
-        tr = self.scorer if isinstance(self.scorer, TreeArrays) else None
-        res = featurize_score(pt, self.spec, idf=self.idf, lr=lr, trees=tr, device="cpu")
+        lr, tr, classes = _split_scorer(self.scorer)
+        res = featurize_score(pt, self.spec, idf=self.idf, lr=lr, trees=tr, device="cpu", classes=classes)
         self._inflight.append((slot, res.raw.numpy().copy()))
 
     def collect(self, copy: bool = True) -> tuple:

@@ -137,12 +137,12 @@ def _serve_group(args, agent, devices, out_topic: str) -> int:
     if os.getenv("KAFKA_BOOTSTRAP_SERVERS", "").startswith("memory://") or os.getenv("FDX_KAFKA", "") == "memory":
         raise SystemExit("--group-clients needs a real Kafka bootstrap (an in-memory broker is per process)")
     fp = agent.fused
-    scorer = make_multi_scorer(fp.spec(True), fp.idf.idf if fp.idf is not None else None, fp.model.scorer(),
+    scorer = make_multi_scorer(fp.spec(True), fp.idf.idf if fp.idf is not None else None, fp.model.serving_scorer(),
                                devices, max_docs=args.batch, max_bytes=args.batch * 4096, depth=3)
     rdv = GroupRendezvous.from_process_group("serve") if D.world_size() > 1 else None
     if rdv is not None and D.rank() > 0:
         log.info("rank %d: scoring process of the group on %s", D.rank(), devices[0])
-        with ScorerPeer(scorer, fp.model.postprocess_numpy, rdv) as peer:
+        with ScorerPeer(scorer, fp.model.serving_postprocess, rdv) as peer:
             st = peer.serve()
         print(json.dumps({"rank": D.rank(), **st}), flush=True)
         return 0
@@ -150,7 +150,7 @@ def _serve_group(args, agent, devices, out_topic: str) -> int:
         start_metrics_server(args.metrics_port)
     log.info("serving %s on %s with %d client processes (%d scoring processes) -> %s", args.model,
              [str(d) for d in devices], args.group_clients, D.world_size(), out_topic)
-    with ConsumerGroup(scorer, fp.model.postprocess_numpy, args.group_clients, batch_max=args.batch,
+    with ConsumerGroup(scorer, fp.model.serving_postprocess, args.group_clients, batch_max=args.batch,
                        max_latency_ms=args.max_latency_ms, max_bytes=args.batch * 4096, rendezvous=rdv) as grp:
         P, m = args.group_clients, args.max_messages
         share = None if m is None else [{"max_messages": m // P + (1 if c < m % P else 0)} for c in range(P)]
