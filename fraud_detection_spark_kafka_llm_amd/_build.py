@@ -312,6 +312,24 @@ def build_mlr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
     return out
 
 
+def build_softprob_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/softprob_selftest.cpp`` + the multi-class boosting host twins (``softprob_cpu.cpp``) as a
+    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
+    ``build_mlr_selftest`` (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("softprob_selftest_asan" if sanitize else "softprob_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "softprob_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "softprob_cpu.cpp"}"\n#include "{CSRC / "tests" / "softprob_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -334,7 +352,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the multinomial logistic-regression host twin")
     ap.add_argument("--cls-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the class-score tail of the featurizer's host twin")
+    ap.add_argument("--softprob-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the multi-class boosting host twins")
     args = ap.parse_args(argv)
+    if args.softprob_selftest:
+        return subprocess.run([str(build_softprob_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.cls_selftest:
         return subprocess.run([str(build_cls_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.mlr_selftest:

@@ -161,6 +161,10 @@ class _Plan:
             fp._scorer = model.class_scorer()     # also of a 2-class model: transform gives Spark's [N, 2]
             res = fp.run(raw.packed(), clean=clean)
             frame = model.attach_outputs(frame, res.raw)
+        elif getattr(model, "isMulticlass", False):
+            # multi:softprob trees: the fused launch has no class-tree tail, so the staged route over
+            # the lazy feature columns above (ops.sparse.score_class_trees)
+            frame = model._transform(frame)
         elif model is not None:
             fp = FusedPipeline(tok, rem, tf, idf, model, self.ngram)
             res = fp.run(raw.packed(), clean=clean)

@@ -15,7 +15,7 @@ from typing import Optional
 import numpy as np
 
 from ..io import spark_format as sf
-from ..ops.text import TreeArrays, TreePaths
+from ..ops.text import ClassTreeArrays, TreeArrays, TreePaths
 
 
 @dataclass
@@ -167,6 +167,14 @@ def ensemble_arrays(trees: list, leaf_payload: str, weights: Optional[np.ndarray
     w = np.ones(len(trees)) if weights is None else np.asarray(weights, dtype=np.float64)
     return TreeArrays(np.concatenate(feats), np.concatenate(thrs), np.concatenate(lefts), np.concatenate(rights),
                       np.concatenate(leaves), np.asarray(roots, np.int32), w, K, cmp_less)
+
+
+def class_ensemble_arrays(trees: list, tree_class, num_classes: int, cmp_less: bool = False) -> ClassTreeArrays:
+    """The flat arrays of a class-grouped ensemble (multi-class boosting): scalar leaf values as
+    ``ensemble_arrays(trees, "value")`` plus the class id of every tree."""
+    flat = ensemble_arrays(trees, "value", None, cmp_less)
+    return ClassTreeArrays(flat.feat, flat.thr, flat.left, flat.right, flat.leaf, flat.roots,
+                           np.asarray(tree_class, dtype=np.int64).reshape(-1), num_classes, cmp_less)
 
 
 def shapley_weights(max_depth: int = TreePaths.MAX_DEPTH) -> np.ndarray:

@@ -8,7 +8,10 @@ ring); from a single process ``num_workers > 1`` launches that many rank process
 (parallel/estimator_dp.py) and returns rank 0's model (identical on every rank).
 
 Outputs follow xgboost.spark: ``rawPrediction = [-margin, margin]``, ``probability = [1-p, p]``,
-``prediction = p > 0.5``. Models persist in the Spark ML layout (metadata + ``data/`` trees) and
+``prediction = p > 0.5``. With ``objective="multi:softprob"`` (chosen by itself, as xgboost.spark does,
+when the objective was not set, no process group is active and a label exceeds 1) the model holds
+``C`` trees per round (models/gbdt_softprob.py): ``rawPrediction`` is the ``[N, C]`` margins,
+``probability`` their max-subtracted softmax, ``prediction`` the first argmax. Models persist in the Spark ML layout (metadata + ``data/`` trees) and
 export XGBoost JSON (``save_xgboost_json``; loadable by ``xgboost.Booster.load_model``).
 """
 from __future__ import annotations
@@ -26,6 +29,9 @@ from .base import Estimator, Param, register
 from .classification import ClassificationModelBase
 from .frame import Frame
 from .tree_model import NODE_FIELDS, Tree, ensemble_arrays, ensemble_paths
+
+
+MULTI_OBJECTIVE = "multi:softprob"
 
 
 class _XGBParams:
@@ -116,8 +122,9 @@ class SparkXGBClassifier(_XGBParams, Estimator):
     def _fit(self, frame: Frame) -> "SparkXGBClassifierModel":
         from ..models.gbdt import GBDTParams, check_sampling, fit_gbdt
 
-        if self.getOrDefault("objective") != "binary:logistic":
-            raise NotImplementedError("only objective='binary:logistic' is supported")
+        objective = self.getOrDefault("objective")
+        if objective not in ("binary:logistic", MULTI_OBJECTIVE):
+            raise NotImplementedError("only objective='binary:logistic' and 'multi:softprob' are supported")
         if self.getOrDefault("sampling_method") != "uniform":
             raise NotImplementedError("only sampling_method='uniform' is supported")
         p = GBDTParams(n_estimators=self.getOrDefault("n_estimators"), max_depth=self.getOrDefault("max_depth"),
@@ -133,6 +140,8 @@ class SparkXGBClassifier(_XGBParams, Estimator):
         check_sampling(p)
         w = frame.column(self.getOrDefault("weight_col")) if self.isSet("weight_col") else None
         X, y = frame.column(self.getFeaturesCol()), frame.column(self.getLabelCol())
+        if objective == MULTI_OBJECTIVE or self._labels_exceed_one(y):
+            return self._fit_softprob(X, y, w, p)
         # validation rows (xgboost.spark's validation_indicator_col): split off before training, so
         # the base score, bins and trees are those of a fit on the remaining rows alone.
         # eval_metric is read only here
@@ -179,12 +188,56 @@ class SparkXGBClassifier(_XGBParams, Estimator):
         return m
 
 
+    def _labels_exceed_one(self, y) -> bool:
+        """Whether the default route must hand over to ``multi:softprob``: this process's labels hold a
+        value above 1 (read on the host: no launch, no collective). An explicit ``binary:logistic``
+        with such a label is an error; under an ambient process group the objective is never chosen
+        here (the ranks see different labels), it has to be set."""
+        from ..parallel import dist as D
+
+        yy = np.asarray(_as_numpy(y), dtype=np.float64).reshape(-1)
+        above = bool(yy.size) and bool(np.nanmax(yy) > 1.0)
+        if not above:
+            return False
+        if self.isSet("objective"):
+            raise ValueError("objective='binary:logistic' needs labels in {0, 1}; the label column holds "
+                             f"{np.nanmax(yy):g} (leave the objective unset or use 'multi:softprob')")
+        if D.is_dist():
+            raise ValueError("the label column holds a value above 1: under a process group the objective is not "
+                             "chosen from the local labels, set objective='multi:softprob'")
+        return True
+
+    def _fit_softprob(self, X, y, w, p) -> "SparkXGBClassifierModel":
+        """The multi-class route (models/gbdt_softprob.py); one process, or one rank of an ambient
+        process group."""
+        from ..models.gbdt_softprob import fit_gbdt_softprob
+        from ..utils.config import default_device
+
+        for name in ("validation_indicator_col", "early_stopping_rounds", "pred_contrib_col"):
+            if self.isSet(name):
+                raise NotImplementedError(f"{name} is not supported with objective='multi:softprob'")
+        if int(self.getOrDefault("num_workers")) > 1:
+            raise NotImplementedError("num_workers > 1 is not supported with objective='multi:softprob' (data "
+                                      "parallelism there runs through the ambient process group)")
+        res = fit_gbdt_softprob(X, y, p, weights=w, device=default_device())
+        m = SparkXGBClassifierModel(res.trees, res.num_features, res.base_margin, num_class=res.num_class, uid=self.uid)
+        m._paramMap.update(self._paramMap)
+        m._paramMap["objective"] = MULTI_OBJECTIVE
+        m.training_seconds = res.train_seconds
+        return m
+
+
 @register("xgboost.spark.core.SparkXGBClassifierModel")
 class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
     _uid_prefix = "SparkXGBClassifierModel"
 
-    def __init__(self, trees=None, num_features: int = 0, base_margin: float = 0.0, **kw):
+    def __init__(self, trees=None, num_features: int = 0, base_margin: float = 0.0, num_class: int = 0,
+                 tree_class=None, **kw):
+        """``num_class``: 0 for a ``binary:logistic`` booster (xgboost's own convention), else the
+        class count of a ``multi:softprob`` booster whose tree ``i`` belongs to class ``tree_class[i]``
+        (default ``i % num_class``, the training order)."""
         super().__init__(**kw)
+        self._set_classes(num_class, tree_class, len(trees or []))
         self._trees = list(trees or [])
         self._num_features = int(num_features)
         self.base_margin = float(base_margin)
@@ -203,7 +256,51 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
     def trees(self) -> list:
         return self._trees
 
+    def _set_classes(self, num_class: int, tree_class, n_trees: int) -> None:
+        from ..ops.sparse import softprob_limits
+
+        self.num_class = int(num_class)
+        self.numClasses = self.num_class if self.num_class > 0 else 2
+        self._tree_class = None
+        self._class_arrays = None
+        if self.num_class == 0:
+            return
+        lim = int(softprob_limits()["max_classes"])
+        if not 2 <= self.num_class <= lim:
+            raise ValueError(f"num_class must be 0 (binary) or lie in 2 .. {lim}, got {num_class}")
+        tc = np.arange(n_trees) % self.num_class if tree_class is None else np.asarray(tree_class, dtype=np.int64)
+        if tc.size != n_trees or (tc.size and (tc.min() < 0 or tc.max() >= self.num_class)):
+            raise ValueError("tree_class needs one class id in 0 .. num_class - 1 per tree")
+        self._tree_class = tc.astype(np.int32)
+
+    @property
+    def isMulticlass(self) -> bool:  # noqa: N802
+        """A ``multi:softprob`` booster (also one of two classes: its outputs are ``[N, 2]`` margins)."""
+        return getattr(self, "num_class", 0) > 0
+
+    def class_tree_scorer(self):
+        """The class-grouped tree list of a ``multi:softprob`` model (``ops.sparse.score_class_trees``)."""
+        from .tree_model import class_ensemble_arrays
+
+        if not self.isMulticlass:
+            raise ValueError("class_tree_scorer() belongs to a multi:softprob model; a binary model has scorer()")
+        if self._class_arrays is None:
+            self._class_arrays = class_ensemble_arrays(self._trees, self._tree_class, self.num_class, cmp_less=True)
+        return self._class_arrays
+
+    def _no_margin(self, what: str):
+        return ValueError(f"{what} describes the single margin of a binary model; this multi:softprob model has "
+                          f"{self.numClasses} classes (use transform / class_tree_scorer())")
+
+    def serving_scorer(self):
+        if self.isMulticlass:
+            raise NotImplementedError("the fused class-tree tail is missing: multi:softprob tree models are served "
+                                      "by transform() only (README, Multi-class boosting)")
+        return self.scorer()
+
     def scorer(self) -> TreeArrays:
+        if self.isMulticlass:
+            raise self._no_margin("scorer()")
         if self._arrays is None:
             # thresholds are midpoints between bin values: "<" and "<=" agree on all seen values;
             # keep XGBoost's "x < split_condition" semantics
@@ -212,6 +309,8 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
 
     def paths(self):
         """TreeSHAP path table of the margin, cached with (and as long as) the scorer's arrays."""
+        if self.isMulticlass:
+            raise self._no_margin("paths()")
         arrays = self.scorer()
         cached = self.__dict__.get("_paths")
         if cached is None or cached[0] is not arrays:
@@ -221,16 +320,50 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
     def contributions(self, features):
         """Feature contributions to the margin; the bias entry includes ``base_margin``, so a row
         sums to ``rawPrediction[:, 1]`` (xgboost's ``pred_contribs``)."""
+        if self.isMulticlass:
+            raise NotImplementedError("TreeSHAP contributions of multi:softprob models are not supported")
         paths = self.paths()
         return self._tree_contributions(features, paths, paths.bias + self.base_margin)
 
+    def _class_raw(self, vc) -> torch.Tensor:
+        from ..ops.sparse import score_class_trees
+
+        return score_class_trees(vc, self.class_tree_scorer())
+
     def _transform(self, frame: Frame) -> Frame:
+        if self.isMulticlass:
+            if self.isSet("pred_contrib_col"):
+                raise NotImplementedError("pred_contrib_col is not supported with objective='multi:softprob'")
+            return self.attach_outputs(frame, self._class_raw(self._features_column(frame)))
         out = super()._transform(frame)
         if self.isSet("pred_contrib_col"):
             out = out.withColumn(self.getOrDefault("pred_contrib_col"), self.contributions(frame))
         return out
 
+    def predict(self, features) -> float:
+        if not self.isMulticlass:
+            return super().predict(features)
+        from .linalg import VectorColumn
+
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return float(self.postprocess(self._class_raw(vc))[2][0])
+
+    def predictProbability(self, features):  # noqa: N802
+        if not self.isMulticlass:
+            return super().predictProbability(features)
+        from .linalg import DenseVector, VectorColumn
+
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self.postprocess(self._class_raw(vc))[1][0].cpu().numpy())
+
     def postprocess(self, raw: torch.Tensor):
+        if self.isMulticlass:
+            if raw.dim() != 2 or raw.shape[1] != self.numClasses:
+                raise ValueError(f"expected [N, {self.numClasses}] class scores")
+            m = raw + self.base_margin
+            e = torch.exp(m - m.max(dim=1, keepdim=True).values)
+            prob = e / e.sum(dim=1, keepdim=True)
+            return m, prob, torch.argmax(prob, dim=1).to(torch.float64)   # (the first argmax on ties)
         m = raw[:, 0] + self.base_margin
         rp = torch.stack([-m, m], dim=1)
         p = torch.sigmoid(m)
@@ -238,6 +371,8 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
         return rp, prob, (p > 0.5).to(torch.float64)
 
     def postprocess_numpy(self, raw: np.ndarray):
+        if self.isMulticlass:
+            return ClassificationModelBase.postprocess_numpy(self, raw)
         m = raw[:, 0] + self.base_margin
         p = np.exp(-m)
         np.add(p, 1.0, out=p)
@@ -265,7 +400,7 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
 
     # ------------------------------------------------------------ persistence
     def _metadata_extra(self):
-        md = {"numFeatures": self._num_features, "numClasses": 2, "numTrees": len(self._trees),
+        md = {"numFeatures": self._num_features, "numClasses": self.numClasses, "numTrees": len(self._trees),
               "baseMargin": self.base_margin}
         if getattr(self, "best_iteration", None) is not None:
             md.update(bestIteration=int(self.best_iteration), bestScore=float(self.best_score),
@@ -283,6 +418,8 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
         booster = self.to_xgboost_json()
         booster["learner"]["attributes"]["fdx_trees"] = json.dumps([t.to_node_rows() for t in self._trees])
         booster["learner"]["attributes"]["fdx_base_margin"] = repr(self.base_margin)
+        if self.isMulticlass:
+            booster["learner"]["attributes"]["fdx_num_class"] = str(self.num_class)
         (d / "part-00000").write_text(json.dumps(booster) + "\n")
         (d / "_SUCCESS").write_text("")
 
@@ -297,10 +434,14 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
                 self._trees = [Tree.from_node_rows(rows) for rows in json.loads(attrs["fdx_trees"])]
                 self.base_margin = float(attrs["fdx_base_margin"])
                 self._num_features = int(booster["learner"]["learner_model_param"]["num_feature"])
+                nc = int(attrs.get("fdx_num_class", 0))
+                self._set_classes(nc, booster["learner"]["gradient_booster"]["model"]["tree_info"] if nc else None,
+                                  len(self._trees))
             else:                                   # a booster written by xgboost itself
                 other = SparkXGBClassifierModel.from_xgboost_json(booster)
                 self._trees, self._num_features, self.base_margin = other._trees, other._num_features, \
                     other.base_margin
+                self._set_classes(other.num_class, other._tree_class, len(self._trees))
         else:
             rows = sf.read_data_parquet(path).to_pylist()
             by_tree: dict = {}
@@ -309,6 +450,7 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
             self._trees = [Tree.from_node_rows(by_tree[k]) for k in sorted(by_tree)]
             self._num_features = int(md.get("numFeatures", 0))
             self.base_margin = float(md.get("baseMargin", 0.0))
+            self._set_classes(0, None, len(self._trees))
         self._arrays = None
         self.training_seconds = 0.0
         self.best_iteration = int(md["bestIteration"]) if "bestIteration" in md else None
@@ -354,10 +496,31 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
                 "tree_param": {"num_deleted": "0", "num_feature": str(self._num_features), "num_nodes": str(n),
                                "size_leaf_vector": "1"},
             })
-        base_p = 1.0 / (1.0 + np.exp(-self.base_margin))
         attrs = {}
         if getattr(self, "best_iteration", None) is not None:       # (strings, as xgboost writes them)
             attrs = {"best_iteration": str(int(self.best_iteration)), "best_score": repr(float(self.best_score))}
+        if self.isMulticlass:
+            # multi:softprob: the base score is the margin itself (no logit), tree_info names each tree's
+            # class and an iteration holds num_class trees: iteration_indptr = [0, C, 2C, ...]
+            nc, tc = str(self.num_class), [int(c) for c in self._tree_class]
+            indptr = sorted(set(range(0, len(tc), self.num_class)) | {len(tc)})
+            return {
+                "learner": {
+                    "attributes": attrs,
+                    "feature_names": [], "feature_types": [],
+                    "gradient_booster": {"model": {"gbtree_model_param": {"num_parallel_tree": "1",
+                                                                          "num_trees": str(len(trees))},
+                                                   "iteration_indptr": indptr,
+                                                   "tree_info": tc, "trees": trees},
+                                         "name": "gbtree"},
+                    "learner_model_param": {"base_score": f"{self.base_margin:.9E}", "boost_from_average": "1",
+                                            "num_class": nc, "num_feature": str(self._num_features),
+                                            "num_target": "1"},
+                    "objective": {"name": MULTI_OBJECTIVE, "softmax_multiclass_param": {"num_class": nc}},
+                },
+                "version": [2, 0, 3],
+            }
+        base_p = 1.0 / (1.0 + np.exp(-self.base_margin))
         return {
             "learner": {
                 "attributes": attrs,
@@ -384,7 +547,9 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
         L = d["learner"]
         nf = int(L["learner_model_param"]["num_feature"])
         bp = float(L["learner_model_param"]["base_score"])
-        base = float(np.log(bp / (1 - bp)))
+        nc = int(L["learner_model_param"].get("num_class", 0) or 0)
+        # (multi:softprob: the base score is the margin, untransformed)
+        base = bp if nc > 0 else float(np.log(bp / (1 - bp)))
         trees = []
         for tj in L["gradient_booster"]["model"]["trees"]:
             lc = np.asarray(tj["left_children"])
@@ -398,4 +563,6 @@ class SparkXGBClassifierModel(_XGBParams, ClassificationModelBase):
             trees.append(Tree(feat, np.where(leaf, 0.0, cond), np.where(leaf, -1, lc).astype(np.int32),
                               np.where(leaf, -1, rc).astype(np.int32), np.stack([val, hess], 1), np.zeros(n),
                               np.asarray(tj["loss_changes"], dtype=np.float64), np.zeros(n, np.int64), val, 0))
+        if nc > 0:
+            return cls(trees, nf, base, num_class=nc, tree_class=L["gradient_booster"]["model"]["tree_info"])
         return cls(trees, nf, base)

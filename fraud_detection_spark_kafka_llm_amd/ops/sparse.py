@@ -340,6 +340,73 @@ def mlr_eval(indptr, idx, val, XS: torch.Tensor, b: torch.Tensor, y: torch.Tenso
     return MlrBlock(out, F, C_, *rows)
 
 
+def softprob_limits() -> dict:
+    """Structural constants of the multi-class boosting kernels: ``max_classes``, workgroup size
+    (``block``), ``wave`` and the hessian floor (``min_hess``)."""
+    return dict(native.lib().softprob_limits())
+
+
+def _check_classes(C_: int) -> None:
+    lim = int(softprob_limits()["max_classes"])
+    if not 2 <= C_ <= lim:
+        raise ValueError(f"the class count must lie in 2 .. {lim}, got {C_}")
+
+
+def softprob_grad(margin: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], g: torch.Tensor,
+                  h: torch.Tensor, threads: int = 0) -> None:
+    """The gradient planes of ``multi:softprob`` in one launch (``csrc/softprob.h``): ``margin`` is
+    ``[C, N]`` fp64, ``y`` ``[N]`` fp32 labels (integers ``0 .. C - 1``; only compared, never an
+    index), ``w`` ``[N]`` fp32 or ``None`` (1.0); ``g`` and ``h`` are ``[C, N]`` fp32 planes whose rows
+    are contiguous (a plane may be a view of a wider buffer) and of which exactly ``[c, :N]`` is written.
+    Everything is checked here, before the launch."""
+    if margin.dim() != 2:
+        raise ValueError("margin is [C, N]")
+    C_, n = int(margin.shape[0]), int(margin.shape[1])
+    _check_classes(C_)
+    for name, t, dt in (("margin", margin, torch.float64), ("g", g, torch.float32), ("h", h, torch.float32)):
+        if t.dtype != dt or t.device != margin.device:
+            raise ValueError(f"{name} must be {dt} on the margins' device")
+        if t.dim() != 2 or tuple(t.shape) != (C_, n):
+            raise ValueError(f"{name} must be [C, N] = [{C_}, {n}], got {tuple(t.shape)}")
+        if (n > 1 and t.stride(1) != 1) or t.stride(0) < n:
+            raise ValueError(f"{name}: the rows of a plane must be contiguous and the planes disjoint")
+    for name, t in (("y", y), ("w", w)):
+        if t is None and name == "w":
+            continue
+        if t.dtype != torch.float32 or t.device != margin.device or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 vector on the margins' device")
+        if t.numel() != n:
+            raise ValueError(f"{name} needs one entry per row ({n}), got {t.numel()}")
+    native.lib().softprob_grad(margin, y, w, g, h, threads)
+
+
+def score_class_trees(vc, arrays, threads: int = 0) -> torch.Tensor:
+    """Raw class scores ``[N, C]`` fp64 of a class-grouped tree list (``ClassTreeArrays``):
+    ``raw[r, c]`` is the sum of the leaf values of the trees of class ``c`` in the order of
+    ``csrc/softprob.h`` (64 lane-strided partials, the xor butterfly); a class without a tree gives
+    ``+0.0``. Everything is checked here, before the launch."""
+    from .text import ClassTreeArrays
+
+    if not isinstance(arrays, ClassTreeArrays):
+        raise TypeError(f"score_class_trees takes ClassTreeArrays, got {type(arrays)}")
+    C_ = int(arrays.num_classes)
+    _check_classes(C_)
+    tc = arrays.tree_class
+    if tc.size != arrays.roots.size:
+        raise ValueError("tree_class needs one entry per tree")
+    if tc.size and (int(tc.min()) < 0 or int(tc.max()) >= C_):
+        raise ValueError(f"a tree's class id lies outside 0 .. {C_ - 1}")
+    if arrays.max_feature() >= vc.size:
+        raise ValueError("tree references a feature beyond the feature space")
+    indptr, idx, val = _csr(vc)
+    dev = indptr.device
+    n = indptr.numel() - 1
+    out = torch.empty((n, C_), dtype=torch.float64, device=dev)
+    t = arrays.tensors(dev)
+    native.lib().score_class_trees(indptr, idx, val, t[:6], t[6], C_, arrays.cmp_less, out, threads)
+    return out
+
+
 def sim_limits() -> dict:
     """Structural constants of the retrieval kernels: largest ``k``, distinct terms of a query held
     in LDS, corpus rows per workgroup chunk, queries per pass over a chunk, wave and workgroup size."""

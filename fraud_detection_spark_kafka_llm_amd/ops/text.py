@@ -279,6 +279,38 @@ class TreeArrays(_DeviceCached):
         return int(self.feat.max()) if self.feat.size else -1
 
 
+class ClassTreeArrays(_DeviceCached):
+    """Flattened class-grouped ensemble (see ``fdx::ClassTreeArgs``): the arrays of ``TreeArrays`` with
+    scalar leaf values (``K = 1``) plus one int32 class id per tree, any assignment. The scorer adds a
+    tree's leaf value into the column of its class (``ops.sparse.score_class_trees``). Not a
+    ``TreeArrays``: the binary scorers and the fused tree tail must not take one."""
+
+    def __init__(self, feat, thr, left, right, leaf, roots, tree_class, num_classes: int, cmp_less: bool):
+        # (the same consistency checks: sizes, children and roots in range)
+        flat = TreeArrays(feat, thr, left, right, leaf, roots, np.ones(np.asarray(roots).size), 1, cmp_less)
+        self.feat, self.thr, self.left, self.right = flat.feat, flat.thr, flat.left, flat.right
+        self.leaf, self.roots, self.cmp_less = flat.leaf, flat.roots, flat.cmp_less
+        tc = np.asarray(tree_class).reshape(-1)
+        if tc.size != self.roots.size:
+            raise ValueError("tree_class needs one entry per tree")
+        if tc.size and (np.any(tc != np.floor(tc)) or tc.min() < -2**31 or tc.max() >= 2**31):
+            raise ValueError("tree_class holds int32 class ids")
+        self.tree_class = np.ascontiguousarray(tc, dtype=np.int32)
+        self.num_classes = int(num_classes)
+
+    @property
+    def num_trees(self) -> int:
+        return int(self.roots.size)
+
+    def max_feature(self) -> int:
+        return int(self.feat.max()) if self.feat.size else -1
+
+    def tensors(self, device) -> list:
+        """(feat, thr, left, right, leaf, roots, tree_class) on ``device``."""
+        return self._cached(device, lambda d: [torch.from_numpy(a).to(d) for a in (
+            self.feat, self.thr, self.left, self.right, self.leaf, self.roots, self.tree_class)])
+
+
 class TreePaths(_DeviceCached):
     """Path table of an ensemble for TreeSHAP (see ``fdx::ContribPaths``; built by
     ``ml.tree_model.ensemble_paths``). An *element* is one distinct feature on one root-to-leaf

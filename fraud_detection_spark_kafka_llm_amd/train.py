@@ -177,6 +177,29 @@ def fit_multinomial_lr(feature_stages: list, label_col: str, datasets: dict, reg
     return out
 
 
+def fit_softprob_xgb(feature_stages: list, label_col: str, datasets: dict, n_estimators: int = 20,
+                     max_depth: int = 5) -> dict:
+    """``SparkXGBClassifier(objective="multi:softprob")`` on the fitted feature stages with ``label_col`` as
+    the class (``datasets`` holds the ``Train`` frame and the frames to score): accuracy per dataset."""
+    from .ml.xgboost import SparkXGBClassifier
+
+    frames = {}
+    for name, df in datasets.items():
+        cur = df
+        for s in feature_stages:
+            cur = s.transform(cur)
+        frames[name] = cur.withColumn("xgb_class", integer_codes(df, label_col))
+    model = SparkXGBClassifier(features_col="features", label_col="xgb_class", objective="multi:softprob",
+                               n_estimators=n_estimators, max_depth=max_depth).fit(frames["Train"])
+    out = {"numClasses": model.numClasses, "numTrees": len(model.trees)}
+    for name, cur in frames.items():
+        pred = model.transform(cur).column("prediction")
+        pred = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
+        out[name] = {"Accuracy": float((pred == cur.column("xgb_class")).mean()) if len(pred) else 0.0}
+        print(f"MultiClassXGBoost {name} accuracy: {out[name]['Accuracy']:.4f}")
+    return out
+
+
 def analyze_word_associations(spark, model: PipelineModel, df: Frame, vocab: list, top_n: int = 10) -> Optional[Frame]:
     """Top-N features by importance -> docs containing the word by label (full dataset, like the
     reference) -> [word, scam_count, non_scam_count, scam_ratio, importance] by importance desc."""
@@ -212,6 +235,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--naive-bayes", action="store_true", help="also train Spark's multinomial NaiveBayes")
     ap.add_argument("--lr-label-col", default=None, metavar="COL",
                     help="also fit a multinomial LogisticRegression on the integer-coded column COL (classes 0 .. C - 1)")
+    ap.add_argument("--xgb-label-col", default=None, metavar="COL",
+                    help="also fit a multi:softprob SparkXGBClassifier on the integer-coded column COL "
+                         "(classes 0 .. C - 1, at most 8)")
     Config.add_cli_args(ap)          # --num-trees, --max-depth, --vocab-size, --seed, --device, --config ...
     args = ap.parse_args(argv)
     cfg = Config.from_cli(args)
@@ -267,6 +293,11 @@ def main(argv=None) -> dict:
             summary["MultinomialLogisticRegression"] = fit_multinomial_lr(
                 next(iter(models.values())).stages[:-1], args.lr_label_col,
                 {"Train": train_df, "Validation": val_df, "Test": test_df})
+        if args.xgb_label_col:
+            summary["MultiClassXGBoost"] = fit_softprob_xgb(
+                next(iter(models.values())).stages[:-1], args.xgb_label_col,
+                {"Train": train_df, "Validation": val_df, "Test": test_df},
+                n_estimators=min(int(cfg.num_trees), 20), max_depth=int(cfg.max_depth))
         with open(os.path.join(args.out_dir, "results.json"), "w") as fh:
             json.dump({"metrics": summary, "word_stats": word_stats,
                        "split": [train_df.count(), val_df.count(), test_df.count()]}, fh, indent=2)

@@ -55,6 +55,7 @@ CHUNK_ENTRY_TEMP = 48.0     # per chunk entry: compaction int64 step + position 
 LEVEL_HIST_BYTES = 16.0     # (g, h) int64 sums per bin per node built in one level
 KEEP_BIT_BYTES = 1.0 / 8.0  # row subsampling: one keep bit per row (grower.Workspace.keepbits)
 COL_MASK_BYTES = 1.0        # column sampling: one byte per feature index and tree level (grower.ColumnSampler)
+SOFTPROB_PLANE_BYTES = 16.0  # multi:softprob: per class and row, the fp64 margin plus the fp32 g and h planes
 RF_LANE_ROW_BYTES = 27.0    # RF: per tree in flight (models/forest_batch.py lanes), its workspace:
                             # digit words, masked digits, row -> node, packed row state, slots
                             # (~0.27 GB per lane at 10M rows, profiles/r4/rf500_sweep_*.json)
@@ -97,13 +98,15 @@ def featurize_bytes(rows: int, nnz: int, text_bytes_per_row: float = DEFAULT_BYT
 def training_bytes(rows: int, nnz: int, hot_features: int = DEFAULT_HOT_FEATURES, total_bins: int = 0,
                    built_nodes: int = DEFAULT_BUILT_NODES, groups: int = DEFAULT_GROUPS,
                    sparse_frac: float = DEFAULT_SPARSE_FRAC, rf_lanes: int = 0, n_val: int = 0,
-                   val_nnz: int = 0, subsample: bool = False, col_features: int = 0, col_depth: int = 6) -> float:
+                   val_nnz: int = 0, subsample: bool = False, col_features: int = 0, col_depth: int = 6,
+                   num_class: int = 0) -> float:
     """Peak bytes of training (GBDT, row-group engine) on ``rows`` rows with ``nnz`` entries.
     ``subsample``: a fit with row subsampling (its keep bits); ``col_features`` > 0: one with column
     sampling over that many feature indices (its per-level byte mask).
     ``rf_lanes`` > 0: a RandomForest with that many trees in flight instead (its CSC work items
     and a workspace per lane on top of the shared state). ``n_val`` > 0: plus the validation set
-    of a monitored GBDT fit (``validation_bytes``)."""
+    of a monitored GBDT fit (``validation_bytes``). ``num_class`` > 0: a ``multi:softprob`` fit of that many
+    classes (models/gbdt_softprob.py), its ``16 C N`` bytes of margin and gradient planes on top."""
     per_entry = CSR_BYTES * CSR_SLACK + ORDER_BYTES + BIN_BYTES + RG_ENTRY_BYTES + RG_EROW_BYTES * sparse_frac
     per_row = ROW_BYTES + 4.0 * row_groups_for(nnz, groups, sparse_frac) + hot_features + LEVEL_ROW_BYTES
     if rf_lanes > 0:
@@ -111,6 +114,8 @@ def training_bytes(rows: int, nnz: int, hot_features: int = DEFAULT_HOT_FEATURES
         per_row += RF_LANE_ROW_BYTES * rf_lanes
     if subsample:
         per_row += KEEP_BIT_BYTES
+    if num_class > 0:
+        per_row += SOFTPROB_PLANE_BYTES * num_class
     return per_entry * nnz + per_row * rows + LEVEL_HIST_BYTES * total_bins * built_nodes * 2 \
         + validation_bytes(n_val, val_nnz) + COL_MASK_BYTES * col_features * col_depth
 
