@@ -330,11 +330,120 @@ static void test_rowgroups() {
   for (size_t i = kept.size(); i < (size_t)N; ++i) EXPECT(list[i] == -7);
 }
 
+// One feature_order_cpu case in buffers of exactly the contracted size, against a scan of the CSR
+// per feature (rows ascending inside a column, b = 0 for count <= 0, 255 from 255 up, else floor).
+template <class V>
+static void layout_order_case(const std::vector<int64_t>& indptr, const std::vector<int32_t>& idx,
+                              const std::vector<V>& counts, int32_t F) {
+  const int64_t rows = (int64_t)indptr.size() - 1, nnz = (int64_t)idx.size();
+  std::vector<int32_t> csc_row(nnz), maxc(F, -1);
+  std::vector<uint8_t> csc_cnt(nnz);
+  std::vector<int64_t> colptr(F + 1, -1), df(F, -1);
+  FeatureOrderArgs<V> a{};
+  a.indptr = indptr.data(); a.idx = idx.data(); a.counts = counts.data(); a.rows = rows; a.nnz = nnz; a.F = F;
+  a.csc_row = csc_row.data(); a.csc_cnt = csc_cnt.data(); a.colptr = colptr.data(); a.df = df.data(); a.maxc = maxc.data();
+  feature_order_cpu<V>(a);
+  int64_t p = 0;
+  for (int32_t f = 0; f < F; ++f) {
+    EXPECT(colptr[f] == p);
+    int64_t nz = 0;
+    int32_t mx = 0;
+    for (int64_t r = 0; r < rows; ++r)
+      for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+        if (idx[e] != f) continue;
+        const double c = (double)counts[e];
+        const int b = c <= 0.0 ? 0 : (c >= 255.0 ? 255 : (int)std::floor(c));
+        EXPECT(p < nnz && csc_row[p] == (int32_t)r && csc_cnt[p] == b);
+        nz += b > 0;
+        mx = std::max(mx, b);
+        ++p;
+      }
+    EXPECT(df[f] == nz && maxc[f] == mx);
+  }
+  EXPECT(p == nnz && colptr[F] == nnz);
+}
+
+// Host twins of the layout kernels (sparse_cpu.cpp): feature order, segment copy, dense scatter and
+// row-block bounds on the smallest shapes with their edges -- empty rows and columns, counts 0, 0.5,
+// 255, 256 and negative, zero-length segments, key offsets that wrap -- in heap buffers that end
+// where the contract ends, against loops written here.
+static void test_layout() {
+  // rows 0, 2 and 5 empty; features 2 and 5 (the last) stored nowhere
+  const std::vector<int64_t> indptr = {0, 0, 2, 2, 5, 6, 6, 8};
+  const std::vector<int32_t> idx = {0, 3, 1, 3, 4, 0, 0, 4};
+  layout_order_case<float>(indptr, idx, {0.0f, 0.5f, 255.0f, 256.0f, -1.0f, 254.9f, 1.0f, 300.5f}, 6);
+  layout_order_case<double>(indptr, idx, {0.0, 0.5, 255.0, 256.0, -1.0, 254.9, 1.0, 300.5}, 6);
+  layout_order_case<int32_t>(indptr, idx, {0, 1, 255, 256, -3, 2147483647, 2, 254}, 6);
+  layout_order_case<int32_t>({0, 1, 1}, {0}, {7}, 1);
+  layout_order_case<float>({0, 0, 0}, {}, {}, 3);              // no entry at all
+
+  // copy_segments: zero-length segments, places in another order, the last one ends the buffers
+  {
+    const std::vector<int64_t> len = {0, 1, 5, 0, 3}, src = {2, 9, 1, 10, 7}, dst = {4, 0, 6, 3, 2};
+    const std::vector<uint8_t> add = {9, 255, 10, 1, 200};
+    std::vector<int32_t> srow(10), drow;
+    std::vector<uint8_t> skey(10), dkey;
+    for (int i = 0; i < 10; ++i) { srow[i] = 1000 + i; skey[i] = (uint8_t)(246 + i); }   // 246 .. 255
+    for (int with_add = 0; with_add < 2; ++with_add) {
+      drow.assign(11, -7);
+      dkey.assign(11, 0xEE);
+      copy_segments_cpu(srow.data(), skey.data(), src.data(), dst.data(), len.data(), (int64_t)len.size(),
+                        with_add ? add.data() : nullptr, drow.data(), dkey.data());
+      std::vector<int32_t> wrow(11, -7);
+      std::vector<uint8_t> wkey(11, 0xEE);
+      for (size_t i = 0; i < len.size(); ++i)
+        for (int64_t k = 0; k < len[i]; ++k) {
+          wrow[dst[i] + k] = srow[src[i] + k];
+          wkey[dst[i] + k] = (uint8_t)((skey[src[i] + k] + (with_add ? add[i] : 0)) & 0xFF);
+        }
+      EXPECT(drow == wrow && dkey == wkey);
+      EXPECT(drow[1] == -7 && dkey[1] == 0xEE && drow[5] == -7 && dkey[5] == 0xEE);   // the gaps
+      EXPECT(!with_add || dkey[6] == (uint8_t)((247 + 10) & 0xFF));                   // wrapped past 255
+    }
+    copy_segments_cpu(srow.data(), skey.data(), src.data(), dst.data(), len.data(), 0, nullptr, drow.data(), dkey.data());
+  }
+
+  // dense_scatter: three rows of 64 cells, a distinct prefill each; the last segment writes the last cell
+  {
+    const int64_t n_pad = 64;
+    const std::vector<int64_t> seg_src = {3, 0, 0}, seg_len = {2, 0, 3};
+    const std::vector<int32_t> row = {0, 31, 63, 5, 62};
+    const std::vector<uint8_t> bin = {1, 2, 3, 4, 5};
+    std::vector<uint8_t> dense(3 * n_pad), want(3 * n_pad);
+    for (int i = 0; i < 3; ++i)
+      for (int64_t c = 0; c < n_pad; ++c) dense[i * n_pad + c] = want[i * n_pad + c] = (uint8_t)(200 + i);
+    for (int i = 0; i < 3; ++i)
+      for (int64_t k = 0; k < seg_len[i]; ++k) want[i * n_pad + row[seg_src[i] + k]] = bin[seg_src[i] + k];
+    dense_scatter_cpu(row.data(), bin.data(), seg_src.data(), seg_len.data(), 3, n_pad, dense.data());
+    EXPECT(dense == want && dense[2 * n_pad + 63] == 3 && dense[n_pad + 5] == 201);
+  }
+
+  // block_bounds: an empty column, one inside a single block, rows at the multiples of the block and
+  // one below them; an unordered subset of the columns; the last block reaches past the rows
+  {
+    const std::vector<int32_t> csc_row = {0, 4, 5, 9, 6, 7, 3};
+    const std::vector<int64_t> colptr = {0, 0, 4, 6, 7};
+    const std::vector<int32_t> cols = {2, 0, 3, 1};
+    for (int32_t nblk : {1, 3}) {
+      const int64_t row_block = 5;
+      std::vector<int64_t> bounds(cols.size() * (nblk + 1), -1);
+      block_bounds_cpu(csc_row.data(), colptr.data(), cols.data(), (int32_t)cols.size(), nblk, row_block, bounds.data());
+      for (size_t i = 0; i < cols.size(); ++i)
+        for (int32_t b = 0; b <= nblk; ++b) {
+          int64_t want = colptr[cols[i]];
+          for (int64_t e = colptr[cols[i]]; e < colptr[cols[i] + 1]; ++e) want += csc_row[e] < b * row_block;
+          EXPECT(bounds[i * (nblk + 1) + b] == want);
+        }
+    }
+  }
+}
+
 int main() {
   test_featurizer();
   test_json();
   test_tree();
   test_rowgroups();
+  test_layout();
   if (g_fail) {
     std::fprintf(stderr, "%d failures\n", g_fail);
     return 1;

@@ -624,7 +624,7 @@ def feature_order(indptr: torch.Tensor, idx: torch.Tensor, counts: torch.Tensor,
     tot = torch.stack(lens).sum(0)
     colptr = torch.zeros(num_features + 1, dtype=torch.int64, device=dev)
     torch.cumsum(tot, 0, out=colptr[1:])
-    df = tot
+    df = torch.zeros(num_features, dtype=torch.int64, device=dev)
     maxc = torch.zeros(num_features, dtype=torch.int32, device=dev)
     before = torch.zeros(num_features, dtype=torch.int64, device=dev)
     # pass 2: sort each block, add its first row, copy its columns into place (one block's
@@ -634,8 +634,10 @@ def feature_order(indptr: torch.Tensor, idx: torch.Tensor, counts: torch.Tensor,
         n = e1 - e0
         brow = torch.zeros(n + pad, dtype=torch.int32, device=dev)
         bcnt = torch.zeros(n + pad, dtype=torch.uint8, device=dev)
-        bcol, _, bmax = _feature_order_one(indptr[r0:r1 + 1] - e0, idx[e0:e1], counts[e0:e1], num_features, brow, bcnt)
+        bcol, bdf, bmax = _feature_order_one(indptr[r0:r1 + 1] - e0, idx[e0:e1], counts[e0:e1], num_features, brow,
+                                             bcnt)
         brow[:n] += r0
+        df += bdf                        # entries with a positive count, as in the one-shot order
         torch.maximum(maxc, bmax, out=maxc)
         C.copy_segments(brow[:n], bcnt[:n], bcol[:-1].contiguous(), (colptr[:-1] + before).contiguous(), ln,
                         row_buf[:nnz], cnt_buf[:nnz], None)
@@ -658,6 +660,7 @@ class IncrementalFeatureOrder:
         self.F, self.dev = int(num_features), torch.device(device)
         self.blocks: list = []               # (block colptr, rows (global), counts u8, n entries)
         self.maxc = torch.zeros(self.F, dtype=torch.int32, device=self.dev)
+        self.df = torch.zeros(self.F, dtype=torch.int64, device=self.dev)    # entries with a positive count
         self.nnz = 0
 
     def add(self, indptr: torch.Tensor, idx: torch.Tensor, counts: torch.Tensor, first_row: int) -> None:
@@ -667,9 +670,10 @@ class IncrementalFeatureOrder:
         n = int(idx.numel())
         brow = torch.zeros(n + self.PAD, dtype=torch.int32, device=self.dev)
         bcnt = torch.zeros(n + self.PAD, dtype=torch.uint8, device=self.dev)
-        bcol, _, bmax = _feature_order_one(indptr, idx, counts, self.F, brow, bcnt)
+        bcol, bdf, bmax = _feature_order_one(indptr, idx, counts, self.F, brow, bcnt)
         if first_row:
             brow[:n] += int(first_row)
+        self.df += bdf
         torch.maximum(self.maxc, bmax, out=self.maxc)
         self.blocks.append((bcol, brow, bcnt, n))
         self.nnz += n
@@ -682,7 +686,7 @@ class IncrementalFeatureOrder:
         torch.cumsum(tot, 0, out=colptr[1:])
         if len(self.blocks) == 1:               # one block: its sort is the CSC
             _, brow, bcnt, n = self.blocks.pop()
-            return FeatureOrder(brow[:n], bcnt[:n], colptr, tot, self.maxc)
+            return FeatureOrder(brow[:n], bcnt[:n], colptr, self.df, self.maxc)
         row_buf = torch.zeros(nnz + self.PAD, dtype=torch.int32, device=dev)
         cnt_buf = torch.zeros(nnz + self.PAD, dtype=torch.uint8, device=dev)
         before = torch.zeros(self.F, dtype=torch.int64, device=dev)
@@ -692,4 +696,4 @@ class IncrementalFeatureOrder:
                             row_buf[:nnz], cnt_buf[:nnz], None)
             before += ln
         self.blocks = []
-        return FeatureOrder(row_buf[:nnz], cnt_buf[:nnz], colptr, tot, self.maxc)
+        return FeatureOrder(row_buf[:nnz], cnt_buf[:nnz], colptr, self.df, self.maxc)

@@ -38,20 +38,21 @@ def vc_from_dense(dense, device="cpu"):
                         torch.tensor(val, dtype=torch.float64, device=device))
 
 
-def test_count_path_bins_and_thresholds():
+@pytest.mark.parametrize("dev", ["cpu", pytest.param("cuda:0", marks=pytest.mark.gpu)])
+def test_count_path_bins_and_thresholds(dev):
     dense, _ = random_counts_matrix(200, 12, 0.3, 0)
-    Q = quantize(vc_from_dense(dense), max_bins=4)
+    Q = quantize(vc_from_dense(dense, device=dev), max_bins=4)
     assert Q.Fa == 12
     for f in range(Q.Fa):
         assert int(Q.nbins[f]) == min(int(dense[:, f].max()), 3) + 1
         assert Q.threshold(f, 0) == 0.5 and Q.threshold(f, 1) == 1.5
     # CSC holds every nonzero once, bins = min(count, 3), rows sorted within a column
-    colptr = Q.colptr.numpy()
+    colptr = Q.colptr.cpu().numpy()
     for f in range(Q.Fa):
-        rows = Q.csc_row[colptr[f]:colptr[f + 1]].numpy()
+        rows = Q.csc_row[colptr[f]:colptr[f + 1]].cpu().numpy()
         assert np.all(np.diff(rows) > 0)
         np.testing.assert_array_equal(rows, np.nonzero(dense[:, f])[0])
-        np.testing.assert_array_equal(Q.bins_of(f).numpy(), np.minimum(dense[rows, f], 3).astype(np.uint8))
+        np.testing.assert_array_equal(Q.bins_of(f).cpu().numpy(), np.minimum(dense[rows, f], 3).astype(np.uint8))
 
 
 def test_generic_path_with_negatives():
@@ -267,8 +268,9 @@ def test_gpu_sampled_rf_pass_equals_build_pass_and_host(nslots, root, lds):
     assert torch.equal(ref, got) and torch.equal(got, href)
 
 
+@pytest.mark.parametrize("dev", ["cpu", pytest.param("cuda:0", marks=pytest.mark.gpu)])
 @pytest.mark.parametrize("light", [True, False])
-def test_work_items_cover_histogram_csc_once_and_wave_order_is_xcd_grouped(monkeypatch, light):
+def test_work_items_cover_histogram_csc_once_and_wave_order_is_xcd_grouped(monkeypatch, light, dev):
     """The histogram CSC holds every entry of the non-dense features once, super-block-major;
     every entry belongs to exactly one item; packed items hold consecutive small features with
     distinct key ranges; an item stays inside its super-block, or (``light``: few-entry features)
@@ -280,17 +282,18 @@ def test_work_items_cover_histogram_csc_once_and_wave_order_is_xcd_grouped(monke
     rng = np.random.default_rng(2)
     n, F = 5000, 40
     dense = (rng.random((n, F)) < np.linspace(0.002, 0.6, F)) * rng.integers(1, 5, (n, F))
-    Q = quantize(vc_from_dense(dense.astype(np.float64)), max_bins=8, chunk=100, super_rows=700, hot_density=0.0)
+    vc = vc_from_dense(dense.astype(np.float64), device=dev)
+    Q = quantize(vc, max_bins=8, chunk=100, super_rows=700, hot_density=0.0)
     assert Q.dense is None and Q.n_super == 8
-    rows, keys = Q.h_row.numpy(), Q.h_key.numpy()
+    rows, keys = Q.h_row.cpu().numpy(), Q.h_key.cpu().numpy()
     assert rows.size == int(Q.colptr[-1])
     # (row, feature, bin) multiset of the histogram CSC == the feature-major CSC
     fid_of = {}
     cover = np.zeros(rows.size, dtype=np.int64)
     kinds = set()
     for grp in Q.groups:
-        st, en = grp.item_start.numpy(), grp.item_end.numpy()
-        f0, meta, blk = grp.item_f0.numpy(), grp.item_meta.numpy(), grp.item_blk.numpy()
+        st, en = grp.item_start.cpu().numpy(), grp.item_end.cpu().numpy()
+        f0, meta, blk = grp.item_f0.cpu().numpy(), grp.item_meta.cpu().numpy(), grp.item_blk.cpu().numpy()
         for i in range(grp.num_items):
             cover[st[i]:en[i]] += 1
             sl2, nf = meta[i] & 0xFF, (meta[i] >> 8) & 0xFF
@@ -306,7 +309,7 @@ def test_work_items_cover_histogram_csc_once_and_wave_order_is_xcd_grouped(monke
                 f = int(f0[i]) + fl
                 assert fl < nf
                 fid_of[e] = (f, int(keys[e]) - int(Q.kbase_host[f]))
-        order = grp.wave_order().numpy()
+        order = grp.wave_order().cpu().numpy()
         used = order[order >= 0]
         assert sorted(used.tolist()) == list(range(grp.num_items))   # every item exactly once
         slots = np.nonzero(order >= 0)[0]
@@ -316,19 +319,20 @@ def test_work_items_cover_histogram_csc_once_and_wave_order_is_xcd_grouped(monke
     assert np.all(cover == 1)
     assert kinds == ({"packed", "single", "column"} if light else {"packed", "single"})
     got = sorted((int(rows[e]), f, b) for e, (f, b) in fid_of.items())
-    colptr, crow, cbin = Q.colptr.numpy(), Q.csc_row.numpy(), Q.csc_bin.numpy()
+    colptr, crow, cbin = Q.colptr.cpu().numpy(), Q.csc_row.cpu().numpy(), Q.csc_bin.cpu().numpy()
     ref = sorted((int(crow[e]), f, int(cbin[e])) for f in range(Q.Fa) for e in range(colptr[f], colptr[f + 1]))
     assert got == ref
     # with a dense block: hot columns leave the histogram CSC, the dense block holds their bins
-    Qh = quantize(vc_from_dense(dense.astype(np.float64)), max_bins=8, chunk=100, super_rows=700, hot_density=0.3)
+    vc = vc_from_dense(dense.astype(np.float64), device=dev)
+    Qh = quantize(vc, max_bins=8, chunk=100, super_rows=700, hot_density=0.3)
     hot = set(Qh.hot.tolist())
     assert hot == {f for f in range(Qh.Fa) if (dense[:, Qh.fid_host[f]] > 0).mean() >= 0.3}
     assert Qh.h_row.numel() == int(Qh.colptr[-1])      # hot columns stay in the CSC (deep levels)
     for grp in Qh.groups:
-        assert not any(int(f) in hot for f in grp.item_f0.numpy())
-    assert {int(f) for grp in Qh.hot_groups for f in grp.item_f0.numpy()} == hot
+        assert not any(int(f) in hot for f in grp.item_f0.cpu().numpy())
+    assert {int(f) for grp in Qh.hot_groups for f in grp.item_f0.cpu().numpy()} == hot
     for d, f in enumerate(Qh.hot.tolist()):
-        np.testing.assert_array_equal(Qh.dense[d, :n].numpy(), np.minimum(dense[:, Qh.fid_host[f]], 7))
+        np.testing.assert_array_equal(Qh.dense[d, :n].cpu().numpy(), np.minimum(dense[:, Qh.fid_host[f]], 7))
     assert wave_order(None, 0, torch.device("cpu")).tolist() == [-1] * 4
 
 
