@@ -934,11 +934,10 @@ __global__ __launch_bounds__(256) void hist_subtract_kernel(const int64_t* paren
 
 // ------------------------------------------------------------------ split search
 // node n's exact sums (level 0 of the fused prologue: from the quantisation's slots)
-// feature_priority of (node n, feature f) as a double (fmix: mix64 of the original feature id looked up)
+// feature_priority of (node n, feature f)
 __device__ __forceinline__ double split_priority(const SplitArgs& a, int n, int f) {
   const int32_t tree = a.node_tree ? a.node_tree[n] : a.tree;
-  if (a.fmix == nullptr) return feature_priority(a.seed, tree, a.node_ids[n], a.fid_orig[f]);
-  return (double)feature_priority_u53_pre(a.seed, tree, a.node_ids[n], a.fmix[a.fid_orig[f]]) * (1.0 / 9007199254740992.0);
+  return feature_priority(a.seed, tree, a.node_ids[n], a.fid_orig[f]);
 }
 
 __device__ __forceinline__ void split_totals(const SplitArgs& a, int n, int64_t* t0, int64_t* t1) {

@@ -23,12 +23,20 @@ through the kernels' host twins), and the host loop ``grow_tree`` (deep trees). 
 machinery (level counters, LevelBatcher, feature shards, the runners' collectives) is in
 models/dp_batch.py, the host-side trees (GrowParams, TreeTable, tree_from_host) in
 models/tree_table.py; both are re-exported here.
+
+``device_tree_steps`` resolves once how a tree runs (``_resolve_tree`` -> ``_Path`` with one
+``_Driver``) and holds only the control flow and the yields; its stages (prologues, ``_open_level``,
+``_level_sample``, ``_hist_out``, ``_level_hist``, ``_level_rows``, ``_split_search``, the two
+``_*_plan_partition``, ``_read_tree``) are module-level helpers that read that record. (A table of
+mix64(feature) for the RF sampler was tried and removed: profiles/r6/rf_dp_busy_fmix_REJECTED.txt.)
 """
 from __future__ import annotations
 
+import enum
 import functools
 import os
-from typing import Optional
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -45,13 +53,9 @@ from .tree_table import GrowParams, PendingTree, TreeTable, _impurity, leaf_valu
 
 NEG_INF = float("-inf")
 MAX_CT = 8                      # column tiles per pass (csrc/tree_kernels.hip launch_hist)
-DENSE_RANGE_ROWS = 32768        # max rows per wave of the dense hot-feature histogram kernel
-
-
-def dense_range_rows(n_rows: int, ngroups: int) -> int:
-    """Rows per wave of the dense hot-feature kernel (fixed: shorter ranges for launches with few
-    feature groups measured no better, profiles/r2_gbdt_knob_sweep.txt)."""
-    return DENSE_RANGE_ROWS
+# rows per wave of the dense hot-feature histogram kernel (fixed: shorter ranges for launches with
+# few feature groups measured no better, profiles/r2_gbdt_knob_sweep.txt)
+DENSE_RANGE_ROWS = 32768
 # levels 0..DENSE_MAX_DEPTH build the hot features' histograms with the dense kernel (every row
 # streamed, slot-masked); deeper levels use their CSC items (only live entries multiplied)
 DENSE_MAX_DEPTH = 2
@@ -80,8 +84,9 @@ PRESELECT = True
 # level's partition instead of a row pass of their own (slot pack / masked digits: ~87 us per level
 # at 10M rows, 173 ms of a 500-tree forest's kernel time, profiles/r5/NOTES.md)
 FUSED_PACK = True
-# RF device levels issue their kernels through the native per-level runner (csrc/bindings_level.cpp
-# RfLevels: hist / split / plan / partition, one host call each) instead of ~20 Python-level calls
+# device levels issue their kernels through the native per-level runner (csrc/bindings_level.cpp
+# RfLevels: hist / split / plan / partition, one host call each) instead of ~20 Python-level calls:
+# _Path.runner, and in one process the fused prologue (_Driver.RUNNER; 0: _Driver.PYTHON)
 NATIVE_LEVELS = True
 # the partition's row pass writes the next level's row-list counts (runner levels, <= 4M rows)
 PARTITION_COUNTS = True
@@ -90,7 +95,7 @@ PARTITION_COUNTS = True
 # flushes with atomics
 RG_PARTIALS = True
 # GBDT trees on the row-group engine, one process or data parallel: the level loop runs in the
-# runner (C++, RfLevels.gbdt_levels; 0: the generic Python loop)
+# runner (C++, RfLevels.gbdt_levels: _Driver.CXX_GBDT; 0: the generic loop of device_tree_steps)
 GBDT_CXX_LEVELS = True
 # ... which, in one process, builds the sibling with fewer rows (not the smaller hessian sum) where
 # the row lists count their own rows (above 4M rows, or PARTITION_COUNTS off): same trees, shorter
@@ -112,7 +117,7 @@ RF_COMPACT = os.environ.get("FDX_RF_COMPACT", "auto")
 DEVICE_LEVELS = True
 PARTITION_WPS = 256  # blocks per column split (device partition)
 # debug: check on the host that every open node of a data-parallel level is built or subtracted
-# (its histogram row is then written before the split search reads it)
+# (its histogram row is then written before the split search reads it; _dp_level_rows)
 LEVEL_CHECKS = os.environ.get("FDX_LEVEL_CHECKS", "0") == "1"
 
 
@@ -237,23 +242,21 @@ class Workspace:
         for s in self._streams[:min(len(launches) - 1, ns)]:
             main.wait_stream(s)
 
-    def dense_groups(self, bt: int, fg: int, keep: Optional[np.ndarray] = None):
-        """(gfid, gdense) device arrays [ngroups * fg] of the hot features with ``bt`` row tiles
-        (optionally only those with ``keep[d]``), -1 padded; cached when ``keep`` is None."""
+    def dense_groups(self, bt: int, fg: int):
+        """(gfid, gdense) device arrays [ngroups * fg] of the hot features with ``bt`` row tiles,
+        -1 padded; cached."""
         key = (bt, fg)
-        if keep is None and key in self._dense_groups:
+        if key in self._dense_groups:
             return self._dense_groups[key]
         Q = self.Q
-        d = np.nonzero((Q.hot_bt == bt) & (keep if keep is not None else True))[0]
+        d = np.nonzero(Q.hot_bt == bt)[0]
         per_wg = fg * self.dense_waves
         ng = (d.size + per_wg - 1) // per_wg * self.dense_waves
         gfid = np.full(ng * fg, -1, dtype=np.int32)
         gden = np.zeros(ng * fg, dtype=np.int32)
         gfid[:d.size] = Q.hot[d]
         gden[:d.size] = d
-        out = (torch.from_numpy(gfid).to(self.dev), torch.from_numpy(gden).to(self.dev))
-        if keep is None:
-            self._dense_groups[key] = out
+        out = self._dense_groups[key] = (torch.from_numpy(gfid).to(self.dev), torch.from_numpy(gden).to(self.dev))
         return out
 
     def gh(self) -> tuple:
@@ -496,7 +499,6 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
     if on_first_wait is not None:
         on_first_wait()
     dev = Q.device
-    mode_rs = 0 if params.mode == 0 else 1
     np_ = _choose_np(params, weight)
     spt = slots_per_tile(np_)
     pass_slots = spt * MAX_CT
@@ -505,16 +507,8 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
 
     ws.row_node.zero_()
     with tracing.span("tree.quant"):
-        seed = int(params.seed)
-        if np_ == 4:
-            C.tree_quant_max(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, Q.n_rows,
-                             ws.maxabs, Q.row0)
-            mx = coll.max(ws.maxabs) if use_coll else ws.maxabs
-            C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 4, mx, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0, float(params.subsample), ws.keepbits(params))
-        else:
-            C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 1, None, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0)
+        _quantise(C, Q, ws, params, tree_index, _TreeInput(g, h, label, weight, bootstrap, margin), np_,
+                  coll if use_coll else None)
     tot = coll.sum(ws.totals) if use_coll else ws.totals
     head = torch.cat([tot, ws.kexp.to(torch.int64)]).cpu().numpy()
     tab = TreeTable(head[:2].astype(np.int64))
@@ -608,33 +602,14 @@ def grow_tree(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int,
             # RF levels read only the sampled features' CSC items (the dense block would stream
             # every hot feature for a handful of sampled ones)
             use_dense = Q.dense is not None and d <= DENSE_MAX_DEPTH and not params.feat_k
-            sel_groups = Q.groups if use_dense else Q.groups + Q.hot_groups
-            hot_keep = None
             for s0, cnt, h_s2n in passes:
                 slot8 = None
                 if d > 0:
                     C.tree_slot8(ws.row_node, node_slot, s0, cnt, ws.slot8, None, None)
                     slot8 = ws.slot8
-                ct = pass_ct(np_, cnt)
-                s2n = up[h_s2n]
-                launches = []
-                for grp in sel_groups:
-                    if grp.num_items == 0:
-                        continue
-                    launches.append(functools.partial(
-                        C.tree_hist_build, grp.item_start, grp.item_end, grp.item_f0, grp.item_meta, grp.wave_order(),
-                        Q.h_row, Q.h_key, slot8, ws.rowdig, h_boff, Q.nbins, s2n, hist_target, h_stride, grp.bt, ct,
-                        np_, feat_mask))
-                if use_dense:
-                    for bt in (1, 2, 4):
-                        fg = C.tree_dense_fg(bt, ct if d > 0 else 1)
-                        gfid, gden = ws.dense_groups(bt, fg, hot_keep)
-                        if gfid.numel():
-                            rr = dense_range_rows(Q.n_rows, gfid.numel() // fg)
-                            launches.append(functools.partial(
-                                C.tree_hist_dense, Q.dense, ws.digp, ws.rowdig, None if d == 0 else ws.slot8_pad,
-                                gfid, gden, h_boff, Q.nbins, s2n, hist_target, h_stride, Q.n_rows, rr, bt, ct, np_))
-                ws.run_concurrent(launches)
+                ws.run_concurrent(_csc_dense_launches(
+                    C, Q, ws, np_, cnt, d == 0, use_dense, _RowState(slot8, ws.rowdig, None), feat_mask,
+                    _HistOut(hist_target, h_boff, h_stride, up[h_s2n])))
         totals, node_ids = up[h_tot], up[h_ids]
         col_kw = {}
         if col is not None:         # (the node stage rides in feat_thr, as RF's per-node sample does)
@@ -833,29 +808,13 @@ def _level_runner(Q: Quantized, ws: Workspace, st: "LevelState", params: GrowPar
                mcw=float(params.min_child), seed=int(params.seed), subsample=float(params.subsample),
                keepbits=ws.keepbits(params),
                F=int(Q.num_features), k=int(params.feat_k),
-               lds=bool(RF_LDS), wps=int(PARTITION_WPS), arena=st.arena, dig16=ws.dig16() if sampled else None,
-               fmix=_feature_mix(Q) if (params.feat_k and FEATURE_MIX) else None)
+               lds=bool(RF_LDS), wps=int(PARTITION_WPS), arena=st.arena, dig16=ws.dig16() if sampled else None)
     col = ColumnSampler.of(Q, ws, params)
     if col is not None:
         cfg.update(col.runner_cfg())
     runner = native.lib().RfLevels(cfg)
     ws._rf_runner = (st, key, runner)
     return runner
-
-
-# the sampler and split search look mix64(feature) up in a table instead of recomputing it: off,
-# the table reads cost more than the hash (rf_window_threshold 24.6 -> 27.2 ms a forest,
-# profiles/r6/rf_dp_busy_fmix_REJECTED.txt); kept for the record, host twins ignore it
-FEATURE_MIX = False
-
-
-def _feature_mix(Q: Quantized) -> torch.Tensor:
-    """mix64(f) over the F features on the device (the RF priorities' per-feature hash, looked up
-    by the sampler and the split search instead of recomputed per node), once per Q."""
-    t = getattr(Q, "_fmix", None)
-    if t is None:
-        t = Q._fmix = native.lib().tree_feature_mix(int(Q.num_features), Q.nbins)
-    return t
 
 
 # the DP runner calls RCCL directly on the process group's communicator (0: through Python)
@@ -914,6 +873,529 @@ def _gbdt_setup(Q, ws, st, params, runner, rg, shards=None, coll=None) -> torch.
     return root
 
 
+class _Driver(enum.Enum):
+    """Who runs a tree's prologue and its levels: exactly one per tree."""
+    CXX_GBDT = "cxx"        # the runner's C++ GBDT loop (_cxx_gbdt_tree): no level of the generic loop
+    RUNNER = "runner"       # the generic loop behind the runner's fused prologue (one process)
+    PYTHON = "python"       # the generic loop behind the prologue issued launch by launch (host twins,
+    #                         data parallel, trees without a runner)
+
+
+class _Path(NamedTuple):
+    """How one tree runs, resolved once (_resolve_tree); every stage below reads it."""
+    np_: int                # digit planes per statistic (_choose_np)
+    build_all: bool         # per-node feature sampling: every open node built, no sibling subtraction
+    sampled: bool           # ... of class counts (np_ = 1): the packed sampled passes
+    presel: bool            # levels >= 1 launch from item lists compacted with the previous plan
+    sel_ids: tuple          # ... the item groups that have items
+    item_groups: list       # the CSC item groups of the sampled passes
+    runner: object          # the native level runner (RfLevels) or None
+    dp: bool                # feature shards: a level splits around a reduce-scatter and an all-gather
+    compact: bool           # ... which carry only the bins of the level's sampled features
+    col: Optional[ColumnSampler]
+    driver: _Driver
+
+
+# what the stages of one tree work on (stream: the one current when the tree started; the forest
+# driver advances a lane inside that lane's stream context)
+_TreeCtx = namedtuple("_TreeCtx", "C Q ws st params tree seed shards coll stream")
+# a tree's row statistics as given: GBDT g, h (or margin and label to compute them from), class
+# counts label / weight / bootstrap
+_TreeInput = namedtuple("_TreeInput", "g h label weight bootstrap margin")
+# a level's feature sample: RF thresholds per open node + union mask (GBDT column sampling: the
+# node stage's thresholds, tree_split_find's arguments in col_kw); compact levels: the sampled
+# features' bin offsets; data parallel: the bins per shard row
+_Sample = namedtuple("_Sample", "thr mask col_kw local Bs")
+# where a level's histogram passes add: tensor, bin offset per feature, row stride, slot -> row
+_HistOut = namedtuple("_HistOut", "target boff stride s2n")
+# what the CSC passes read per row: slot bytes (None: every row in slot 0), digit words, the
+# sampled passes' packed word (None: the root kernel on ``dig``)
+_RowState = namedtuple("_RowState", "slot8 dig pack")
+
+
+# one level of the generic loop as the host sizes it (the previous plan's counts). cur: parity of
+# the ping-pong level buffers; per_xcd: sampled item group -> its largest per-XCD active-item count
+# (PRESELECT, d > 0); more: a level follows; open / totals: the open nodes' ids and exact sums
+_Level = namedtuple("_Level", "d cur n_open n_build per_xcd more open totals n_open_ptr")
+
+
+def _resolve_tree(Q, ws, params, tree_index, inp: _TreeInput, coll, shards) -> tuple:
+    """(_TreeCtx, _Path) of one tree: level state, runner and driver."""
+    dev = Q.device
+    cuda = dev.type == "cuda"
+    np_ = _choose_np(params, inp.weight)
+    build_all = bool(params.feat_k)
+    sampled = build_all and np_ == 1
+    # RF levels >= 1: the next level's feature sample and its active-item lists are queued right
+    # after the plan, so the per-XCD item counts reach the host with the level's counts and each
+    # histogram pass launches one wave per active item (no grid of ~300K mostly idle wave slots)
+    presel = PRESELECT and sampled and cuda
+    item_groups = (Q.groups + Q.hot_groups) if sampled else []
+    sel_ids = tuple(gi for gi, grp in enumerate(item_groups) if grp.num_items) if presel else ()
+    st = getattr(ws, "_levels", None)
+    if st is None or st.max_depth != params.max_depth or st.n_sel != len(sel_ids):
+        st = ws._levels = LevelState(Q, params.max_depth, len(sel_ids))
+    # the native runner: RF levels and GBDT levels (any world size). A single process also fuses
+    # the GBDT prologue and the split + plan; under data parallelism the quantisation max is an
+    # all-reduce and the levels split around the reduce-scatter / all-gather
+    gbdt_native = NATIVE_LEVELS and cuda and params.mode == 0 and inp.weight is None and not build_all
+    # (the runner's level 0 completes the root's sums: at least one level)
+    runner = _level_runner(Q, ws, st, params, item_groups, sampled) \
+        if (NATIVE_LEVELS and cuda and (sampled or gbdt_native) and params.max_depth >= 1) else None
+    dp = shards is not None
+    fused_prologue = runner is not None and not dp and coll is None
+    # GBDT rounds on the row-group engine, in one process or data parallel: the level loop runs in
+    # the runner (RfLevels.gbdt_levels; data parallel: around the level's collectives, RCCL called
+    # by the runner or Python callbacks)
+    if (runner is not None and (dp or fused_prologue) and gbdt_native and GBDT_CXX_LEVELS and np_ == 4 and
+            inp.margin is not None and inp.g is None and ws.rowgroups() is not None):
+        driver = _Driver.CXX_GBDT
+    else:
+        driver = _Driver.RUNNER if fused_prologue else _Driver.PYTHON
+    # RF under data parallelism: each level reduce-scatters only its sampled features' bins; level
+    # d + 1's sample and layout are computed right after level d's plan, so their shard sizes reach
+    # the host with the level's counts (one wait per level; the root's before the loop)
+    compact = dp and build_all and 0 < params.feat_k < Q.num_features and \
+        (RF_COMPACT == "1" or (RF_COMPACT == "auto" and shards.S > 1))
+    cx = _TreeCtx(native.lib(), Q, ws, st, params, int(tree_index), int(params.seed), shards, coll,
+                  torch.cuda.current_stream(dev) if cuda else None)
+    return cx, _Path(np_, build_all, sampled, presel, sel_ids, item_groups, runner, dp, compact,
+                     ColumnSampler.of(Q, ws, params), driver)
+
+
+def _quantise(C, Q, ws, params, tree_index, inp: _TreeInput, np_: int, coll, max_only: bool = False) -> None:
+    """The tree's quantisation launch by launch: max |statistic| into ws.maxabs (all-reduced under
+    ``coll``) -> digits, exponents and totals (``max_only``: left to the runner's prologue); class
+    counts in one plane need no max."""
+    seed, mode_rs, mx = int(params.seed), 0 if params.mode == 0 else 1, None
+    if np_ == 4:
+        C.tree_quant_max(inp.g, inp.h, inp.label, inp.weight, seed, int(tree_index), bool(inp.bootstrap), mode_rs,
+                         Q.n_rows, ws.maxabs, Q.row0)
+        mx = coll.max(ws.maxabs) if coll is not None else ws.maxabs
+    if not max_only:
+        C.tree_quant(inp.g, inp.h, inp.label, inp.weight, seed, int(tree_index), bool(inp.bootstrap), mode_rs, np_, mx,
+                     ws.rowdig, ws.kexp, ws.totals, ws.digp, Q.row0,
+                     *((float(params.subsample), ws.keepbits(params)) if np_ == 4 else ()))
+
+
+def _runner_prologue(cx: _TreeCtx, p: _Path, inp: _TreeInput) -> torch.Tensor:
+    """Driver RUNNER: gradients, max, arena image, zeroed root histogram and quantisation in the
+    runner's prologue (2 launches for a GBDT round); the root's sums stay in the quantisation's
+    slots, completed by the runner's level 0. Returns the root histogram."""
+    Q, ws, st, runner = cx.Q, cx.ws, cx.st, p.runner
+    pre_hist = torch.empty((1, Q.TB, 2), dtype=torch.int64, device=Q.device)     # zeroed by the prologue
+    with tracing.span("tree.quant"):
+        # (the dense-block digit planes only feed the MFMA dense path, off with the row groups)
+        digp = ws.digp if (ws.digp is not None and not p.build_all and ws.rowgroups() is None) else None
+        if p.np_ == 4 and inp.margin is not None and inp.g is None:
+            g, h = ws.gh()
+            runner.prologue(inp.margin, g, h, inp.label, None, cx.tree, False, 4, None, ws.totals, digp, Q.row0,
+                            pre_hist, st.arena_init_dev)
+        else:
+            # arena image first: the quantisation adds the root totals into it
+            st.arena.copy_(st.arena_init, non_blocking=True)
+            _quantise(cx.C, Q, ws, cx.params, cx.tree, inp, p.np_, None, max_only=True)
+            runner.prologue(None, inp.g, inp.h, inp.label, inp.weight, cx.tree, bool(inp.bootstrap), p.np_,
+                            ws.maxabs if p.np_ == 4 else None, ws.totals, digp, Q.row0, pre_hist, None)
+    if p.col is not None:
+        runner.col_begin(cx.tree)
+    return pre_hist
+
+
+def _python_prologue(cx: _TreeCtx, p: _Path, inp: _TreeInput) -> None:
+    """Driver PYTHON: gradients, quantisation, arena image and root (node 0, open list [0] with the
+    exact totals, no host round trip; under data parallelism the totals are summed by the root
+    level's reduce-scatter, LaneBufs.tot_bin), one launch each."""
+    C, ws, st, coll = cx.C, cx.ws, cx.st, cx.coll
+    if inp.margin is not None and inp.g is None:
+        g, h = ws.gh()
+        C.tree_logistic_grad(inp.margin, inp.label, inp.weight, g, h)
+        inp = inp._replace(g=g, h=h)
+    ws.row_node.zero_()
+    with tracing.span("tree.quant"):
+        _quantise(C, cx.Q, ws, cx.params, cx.tree, inp, p.np_, coll)
+    st.arena.copy_(st.arena_init, non_blocking=True)
+    st.open[0][:1].zero_()
+    if not p.dp:
+        tot = coll.sum(ws.totals) if coll is not None else ws.totals
+        st.stats[0].copy_(tot)
+        st.totals[0][:1].copy_(tot[None])
+    # GBDT column sampling: the tree's and every level's stage thresholds, queued behind the prologue
+    if p.col is not None and p.runner is not None:
+        p.runner.col_begin(cx.tree)
+    elif p.col is not None:
+        p.col.begin(C, cx.seed, cx.tree)
+
+
+def _cxx_gbdt_tree(cx: _TreeCtx, p: _Path, inp: _TreeInput, on_first_wait) -> None:
+    """Driver CXX_GBDT, the whole tree: the prologue (gradients + max |g|, |h|, all-reduced by the
+    runner under data parallelism + arena image + the root histogram or the root's send region
+    zeroed, then the quantisation), level 0 queued, the previous tree's host table built while it
+    runs (``on_first_wait``), then levels 1.. with the host waits inside the runner: the launches
+    and trees of the generic loop."""
+    Q, ws, st, runner = cx.Q, cx.ws, cx.st, p.runner
+    with tracing.span("tree.quant"):
+        root_zero = _gbdt_setup(Q, ws, st, cx.params, runner, ws.rowgroups(), cx.shards, cx.coll)
+        g, h = ws.gh()
+        runner.prologue(inp.margin, g, h, inp.label, None, cx.tree, False, 4, None, ws.totals, None, Q.row0,
+                        root_zero, st.arena_init_dev)
+    if p.col is not None:
+        runner.col_begin(cx.tree)
+    runner.gbdt_root(cx.tree)
+    if on_first_wait is not None:
+        on_first_wait()
+    shape = runner.gbdt_levels(cx.tree)
+    for j in range(0, len(shape), 2):
+        LEVEL_STATS["levels"] += 1
+        LEVEL_STATS["built_nodes"] += shape[j + 1]
+        LEVEL_STATS["hist_bytes"] += shape[j + 1] * Q.TB * 16
+
+
+def _open_level(cx: _TreeCtx, p: _Path, d: int) -> Optional[_Level]:
+    """Level ``d`` as the host sizes it: the root, or the previous plan's counts (waited for by the
+    caller); None when no node is open. Counts the level in LEVEL_STATS."""
+    st, cur = cx.st, d % 2
+    n_open = n_build = 1
+    per_xcd = {}
+    if d > 0:
+        cnt = st.counts_host[d - 1].tolist()
+        n_open, n_build = int(cnt[1]), int(cnt[2])
+        if n_open == 0:
+            return None
+        for j, gi in enumerate(p.sel_ids):      # largest per-XCD active-item count of each sampled group
+            active = cnt[4 + 8 * j: 12 + 8 * j]
+            per_xcd[gi] = max(active)
+            if per_xcd[gi]:           # (launch_hist: (npx + 3) / 4 x 8 workgroups of 4 waves)
+                LEVEL_STATS["listed_passes"] += 1
+                LEVEL_STATS["listed_active_items"] += sum(active)
+                LEVEL_STATS["listed_grid_waves"] += (per_xcd[gi] + 3) // 4 * 8 * 4
+    LEVEL_STATS["levels"] += 1
+    LEVEL_STATS["built_nodes"] += n_build
+    LEVEL_STATS["hist_bytes"] += n_build * cx.Q.TB * 16          # (g, h) int64 partials of the built nodes
+    totals = st.totals[cur][:n_open]
+    if d == 0 and p.driver is _Driver.RUNNER:
+        totals = st.stats[:1]             # (unread: the runner sums the prologue's root slots)
+    return _Level(d, cur, n_open, n_build, per_xcd, d + 1 < cx.params.max_depth, st.open[cur][:n_open], totals,
+                  st.one if d == 0 else st.counts[d - 1, 1:2])
+
+
+def _level_sample(cx: _TreeCtx, p: _Path, lv: _Level) -> _Sample:
+    """RF: the exact k-of-F feature sample per open node and the level's union mask (compact and
+    preselected levels: queued with the previous plan). GBDT column sampling: the node stage."""
+    C, Q, st = cx.C, cx.Q, cx.st
+    thr = mask = local = None
+    Bs = cx.shards.Bs if p.dp else None
+    if p.compact:
+        thr, mask, local, Bs = cx.shards.compact_level(lv.cur, lv.n_open)
+    elif p.sel_ids and lv.d > 0:
+        thr, mask = st.rf_thr[lv.cur][:lv.n_open], st.rf_mask[lv.cur]
+    elif p.build_all:
+        thr = torch.empty(lv.n_open, dtype=torch.float64, device=Q.device)
+        mask = torch.empty(Q.Fa, dtype=torch.uint8, device=Q.device)
+        C.tree_rf_sample(cx.seed, cx.tree, lv.open, int(Q.num_features), int(cx.params.feat_k), Q.fid_orig, thr, mask,
+                         None)
+    col_kw = {}
+    if p.col is not None and p.runner is not None:
+        p.runner.col_level(lv.d, lv.open, cx.tree)       # (node stage queued; find() reads the tables)
+    elif p.col is not None:
+        thr, col_kw = p.col.level_args(C, cx.seed, cx.tree, lv.d, lv.open)
+    return _Sample(thr, mask, col_kw, local, Bs)
+
+
+def _hist_out(cx: _TreeCtx, p: _Path, lv: _Level, smp: _Sample, bufs, pre_hist) -> _HistOut:
+    """One process: the level's [n_open, TB, 2] histograms (``pre_hist`` when the previous level
+    queued their zero fill). Data parallel: this tree's rows of the batch's shard-major send buffer
+    (``bufs``, a LaneBufs), slot k -> partial row k; compact levels send only the sampled bins."""
+    Q, st = cx.Q, cx.st
+    if p.dp:
+        target = bufs.prepare(cx.ws.totals if lv.d == 0 else None)
+        if p.runner is not None:      # (the runner's kernels add the shard offsets themselves)
+            boff = smp.local if p.compact else cx.shards._local
+        else:
+            boff = cx.shards.boff_batched(bufs.shard_bins, smp.local)
+        return _HistOut(target, boff, bufs.Bs, cx.ws.iota(lv.n_build))
+    if pre_hist is not None and pre_hist.shape[0] >= lv.n_open:
+        hist = pre_hist[:lv.n_open]
+    else:
+        hist = torch.zeros((lv.n_open, Q.TB, 2), dtype=torch.int64, device=Q.device)
+    return _HistOut(hist, Q.boff, Q.TB, st.s2n[:lv.n_build] if lv.d > 0 else st.zero1)
+
+
+def _row_pass(cx: _TreeCtx, p: _Path, lv: _Level, rg) -> _RowState:
+    """The row pass in front of a level's CSC passes (none at the root, on the row-group engine,
+    which lists the built rows from row_node itself, and on sampled levels with FUSED_PACK, which
+    read the packed row state the previous level's partition wrote). A single built node: the
+    passes run the root kernel on digit words zeroed outside it (no per-entry slot gather, no
+    compaction; zero rows add nothing)."""
+    C, ws, st = cx.C, cx.ws, cx.st
+    if lv.d == 0:
+        return _RowState(None, ws.rowdig, None)
+    fused = p.sampled and FUSED_PACK
+    single = lv.n_build == 1 and rg is None and not fused
+    if single and getattr(ws, "rowdig_masked", None) is None:
+        ws.rowdig_masked = torch.empty_like(ws.rowdig)
+    if rg is None and not fused:
+        if p.sampled and not single:
+            C.tree_slot_pack(ws.row_node, st.node_slot, lv.n_build, ws.rowdig, ws.rowpack())
+        else:
+            C.tree_slot8(ws.row_node, st.node_slot, 0, lv.n_build, ws.slot8, ws.rowdig if single else None,
+                         ws.rowdig_masked if single else None)
+    pack = ws.rowpack() if (p.sampled and not single) else None
+    return _RowState(None, ws.rowdig_masked, pack) if single else _RowState(ws.slot8, ws.rowdig, pack)
+
+
+def _rowgroup_pass(cx: _TreeCtx, p: _Path, lv: _Level, rg, out: _HistOut, bufs, counted: bool) -> None:
+    """GBDT: the level's histograms from the row-group CSR (root: every row; below: the row lists
+    of the built nodes). ``counted``: the previous partition wrote the lists' counts."""
+    C, Q, ws, st = cx.C, cx.Q, cx.ws, cx.st
+    shard_args = (cx.shards.bin_lo, bufs.shard_bins) if p.dp else (None, 0)
+    root = lv.d == 0
+    # per-workgroup partial tables summed by one reduction instead of every workgroup's atomics on
+    # the same bins (RgHistArgs part); the listed levels have their own, smaller work table
+    wtab = rg.work() if root else rg.list_work()
+    part = dict(part=ws.rg_part(rg, rg.list_work()), wg_first=rg.work_first() if root else rg.list_work_first()) \
+        if (RG_PARTIALS and Q.device.type == "cuda") else {}
+    if root:
+        C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, p.np_, None, None, None, 1, rg.gmode, wtab, out.s2n,
+                       out.target, out.stride, *shard_args, RG_DBG, **rg.em_args(), **part)
+        return
+    # one built node: every row's digit words zeroed outside it, for the entry-major pass of the
+    # sparse groups (taken when the node is large)
+    emdig = ws.rg_emdig() if (lv.n_build == 1 and rg.erow is not None and qmod.RG_EM_MIN_FRAC <= 1.0) else None
+    C.tree_rg_list(ws.row_node, st.node_slot, None, Q.n_rows, lv.n_build, ws.rg_work, ws.rg_start, ws.rg_list,
+                   ws.rowdig, ws.rg_listdig, emdig, counted=counted, keepbits=ws.keepbits(cx.params))
+    C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, p.np_, ws.rg_list, ws.rg_start, ws.rg_listdig,
+                   lv.n_build, rg.gmode, wtab, out.s2n, out.target, out.stride, *shard_args, RG_DBG,
+                   **(rg.em_args(emdig) if emdig is not None else {}), **part)
+
+
+def _sampled_lists(cx: _TreeCtx, p: _Path, lv: _Level) -> list:
+    """Per item group of a sampled pass its (item list, count, per-XCD launch size): preselected
+    (exactly one wave per active item, the list built with the previous level's plan); compacted
+    by the pass itself while few items are active (<= LISTED_MAX_NODES open nodes: ~0.16 vs
+    0.19 ms at the root; with more, its fixed grid balances worse than a wave per slot,
+    profiles/r3s3/rf_probe_chunks.txt); or (None, None, -1): a wave per item slot."""
+    out = []
+    for gi, grp in enumerate(p.item_groups):
+        if grp.num_items and p.sel_ids and lv.d > 0:
+            j = p.sel_ids.index(gi)
+            out.append((cx.ws.item_list(gi, grp)[0], cx.st.counts[lv.d - 1, 4 + 8 * j: 12 + 8 * j], lv.per_xcd[gi]))
+        elif grp.num_items and lv.n_open <= LISTED_MAX_NODES:
+            out.append((*cx.ws.item_list(gi, grp), -1))
+        else:
+            out.append((None, None, -1))
+    return out
+
+
+def _sampled_pass(cx: _TreeCtx, p: _Path, lv: _Level, feat_mask, rows: _RowState, out: _HistOut, bufs) -> None:
+    """RF: the class-count histograms of the sampled features' CSC items, one runner call or one
+    launch per item group on the side streams."""
+    C, Q = cx.C, cx.Q
+    lists = _sampled_lists(cx, p, lv)
+    if p.runner is not None:
+        p.runner.hist(lv.n_build, out.target, out.boff, feat_mask, out.s2n, rows.pack, [t[0] for t in lists],
+                      [t[1] for t in lists], [t[2] for t in lists], cx.shards._shard_of if p.dp else None,
+                      bufs.shard_bins if p.dp else 0)
+        return
+    ct = pass_ct(p.np_, lv.n_build)
+    cx.ws.run_concurrent([functools.partial(
+        C.tree_hist_sampled, grp.item_start, grp.item_end, grp.item_f0, grp.item_meta, grp.wave_order(), Q.h_row,
+        Q.h_key, rows.pack, rows.dig, out.boff, Q.nbins, out.s2n, out.target, out.stride, grp.bt, ct, feat_mask, lst,
+        cnt, RF_LDS, npx) for grp, (lst, cnt, npx) in zip(p.item_groups, lists) if grp.num_items])
+
+
+def _csc_dense_launches(C, Q, ws, np_: int, n_slots: int, root: bool, use_dense: bool, rows: _RowState, feat_mask,
+                        out: _HistOut) -> list:
+    """The launches of one CSC histogram pass over ``n_slots`` node slots: every item group's
+    (``use_dense``: the cold features' only, the hot features streamed from the dense block)."""
+    ct = pass_ct(np_, n_slots)
+    launches = []
+    for grp in (Q.groups if use_dense else Q.groups + Q.hot_groups):
+        if grp.num_items:
+            launches.append(functools.partial(
+                C.tree_hist_build, grp.item_start, grp.item_end, grp.item_f0, grp.item_meta, grp.wave_order(),
+                Q.h_row, Q.h_key, rows.slot8, rows.dig, out.boff, Q.nbins, out.s2n, out.target, out.stride, grp.bt, ct,
+                np_, feat_mask))
+    if use_dense:
+        for bt in (1, 2, 4):
+            fg = C.tree_dense_fg(bt, 1 if root else ct)
+            gfid, gden = ws.dense_groups(bt, fg)
+            if gfid.numel():
+                launches.append(functools.partial(
+                    C.tree_hist_dense, Q.dense, ws.digp, ws.rowdig, None if root else ws.slot8_pad, gfid, gden,
+                    out.boff, Q.nbins, out.s2n, out.target, out.stride, Q.n_rows, DENSE_RANGE_ROWS, bt, ct, np_))
+    return launches
+
+
+def _level_hist(cx: _TreeCtx, p: _Path, lv: _Level, smp: _Sample, out: _HistOut, bufs, rg, counted: bool) -> None:
+    """The histograms of the level's built nodes into ``out``: the row-group engine (``rg``), the
+    sampled RF passes, or the CSC items plus, down to DENSE_MAX_DEPTH, the dense block."""
+    rows = _row_pass(cx, p, lv, rg)
+    if rg is not None:
+        _rowgroup_pass(cx, p, lv, rg, out, bufs, counted)
+    elif p.sampled:
+        _sampled_pass(cx, p, lv, smp.mask, rows, out, bufs)
+    else:
+        # (RF levels read only the sampled features' CSC items)
+        use_dense = cx.Q.dense is not None and lv.d <= DENSE_MAX_DEPTH and not p.build_all
+        cx.ws.run_concurrent(_csc_dense_launches(cx.C, cx.Q, cx.ws, p.np_, lv.n_build, lv.d == 0, use_dense, rows,
+                                                 smp.mask, out))
+
+
+def _level_rows(cx: _TreeCtx, p: _Path, lv: _Level, out: _HistOut, bufs, prev: tuple) -> tuple:
+    """(the level's histograms, the row of each open node or None = its index), the larger siblings
+    subtracted from ``prev`` (the previous level's pair) unless the runner does it in its split
+    search (one process: split_plan). Data parallel, after the reduce-scatter: rows at stride Bs,
+    read in place by the split search; the root also takes its reduced totals."""
+    C, st, nb = cx.C, cx.st, lv.n_build
+    subtract = lv.d > 0 and not p.build_all
+    if not p.dp:
+        if subtract and p.runner is None:
+            C.tree_hist_subtract(prev[0], out.target, st.sub_dst[:nb], st.sub_par[:nb], st.sub_sib[:nb], cx.Q.TB)
+        return out.target, None
+    if lv.d == 0:
+        tot = bufs.reduced_totals()
+        st.stats[0].copy_(tot)
+        lv.totals.copy_(tot[None])
+    if not subtract:
+        # every open node built, slot k = open node k (tree.h level_plan): the reduced rows ARE
+        # the level's histograms
+        return bufs.mine(), None
+    # the built rows stay where the collective wrote them and the subtraction fills rows after
+    # them: per open node its row (tree.h LevelRowsArgs), no copy
+    C.tree_level_rows(st.s2n, st.sub_dst, st.sub_par, prev[1], nb, bufs.row0, bufs.sub_base, st.row_of[lv.cur],
+                      st.dst_row, st.par_row, st.sib_row)
+    if LEVEL_CHECKS:
+        n_sub = int((st.sub_dst[:nb] >= 0).sum())
+        assert nb + n_sub == lv.n_open, (lv.d, nb, n_sub, lv.n_open)
+    C.tree_hist_subtract(prev[0], bufs.out, st.dst_row[:nb], st.par_row[:nb], st.sib_row[:nb], bufs.Bs)
+    return bufs.out, st.row_of[lv.cur][:lv.n_open]
+
+
+def _split_search(cx: _TreeCtx, p: _Path, lv: _Level, smp: _Sample, hist, bufs, row_of):
+    """The best split per open node over this rank's features. One process: the [n_open, 5]
+    tuples (with a runner only their buffer: split_plan searches, reduces and plans in 2
+    launches). Data parallel: this shard's tuples into ``bufs.ag_in`` for the all-gather (None)."""
+    C, Q, ws, sh = cx.C, cx.Q, cx.ws, cx.shards
+    if not p.dp:
+        if p.runner is None:
+            return _best_splits(C, hist, lv.totals, Q.boff, Q.nbins, Q.zbin, Q.fid_orig, lv.open, ws.kexp, cx.params,
+                                smp.thr, cx.tree, Q.Fa, 0, cache=ws.split_cache, **smp.col_kw)
+        packed = ws.split_cache.get(("out", lv.n_open))
+        if packed is None:
+            packed = ws.split_cache[("out", lv.n_open)] = torch.empty((lv.n_open, 5), dtype=torch.int64,
+                                                                      device=Q.device)
+        return packed
+    boff = smp.local[sh.f0: sh.f0 + sh.Fa + 1] if p.compact else sh.boff
+    if p.runner is not None:
+        p.runner.split(hist, lv.totals, boff, sh.nbins, sh.zbin, sh.fid_orig, lv.open, smp.thr, cx.tree, sh.f0,
+                       bufs.ag_in, row_of, _wide_features(sh.nbins, sh.Fa), lv.d if p.col is not None else -1)
+    else:
+        _best_splits(C, hist, lv.totals, boff, sh.nbins, sh.zbin, sh.fid_orig, lv.open, ws.kexp, cx.params, smp.thr,
+                     cx.tree, sh.Fa, sh.f0, cache=ws.split_cache, out=bufs.ag_in, row_of=row_of, **smp.col_kw)
+    return None
+
+
+def _runner_plan_partition(cx: _TreeCtx, p: _Path, lv: _Level, smp: _Sample, hist, packed, prev_hist, rg) -> tuple:
+    """Runner levels: (split search and) plan, the event the host waits on for the next level's
+    counts, the partition. Returns (event, the next level's histograms zeroed by the partition or
+    None, whether its row pass wrote the next level's row-list counts)."""
+    Q, ws, st, sh, runner = cx.Q, cx.ws, cx.st, cx.shards, p.runner
+    d, n_open, nxt = lv.d, lv.n_open, 1 - lv.cur
+    sample_next = lv.more and (p.compact or bool(p.sel_ids))
+    thr_n = mask_n = None
+    lay = (None,) * 5 + (0,)
+    if sample_next and p.compact:
+        thr_n, mask_n = sh.compact_thr(nxt, 2 * n_open), sh.compact_mask(nxt)
+        lay = (sh._fs_dev, Q.nbins, sh._local_c[nxt], sh._sizes[nxt], sh.sizes_host[nxt], sh.max_shard_features)
+    elif sample_next:
+        thr_n, mask_n = st.rf_thr[nxt], st.rf_mask[nxt]
+    sel = [ws.item_list(gi, grp)[0] if gi in p.sel_ids else None for gi, grp in enumerate(p.item_groups)] \
+        if (p.sel_ids and lv.more) else []
+    if p.dp:
+        runner.plan(d, n_open, packed, lv.open, lv.n_open_ptr, st.open[nxt], st.totals[nxt], cx.tree, sample_next,
+                    thr_n, mask_n, *lay, sel)
+    else:
+        fused_sub = d > 0 and not p.build_all
+        runner.split_plan(d, n_open, hist, lv.totals, Q.boff, smp.thr, cx.tree, packed, _wide_features(Q.nbins, Q.Fa),
+                          lv.open, lv.n_open_ptr, st.open[nxt], st.totals[nxt], sample_next, thr_n, mask_n, sel,
+                          prev_hist if fused_sub else None)
+    ev = st.record_event(cx.stream)
+    zero = None
+    if not p.dp and lv.more and not p.build_all:
+        zero = torch.empty((2 * n_open, Q.TB, 2), dtype=torch.int64, device=Q.device)
+    counted = bool(lv.more and rg is not None and PARTITION_COUNTS and cx.C.tree_partition_counts_ok(Q.n_rows))
+    with tracing.span("tree.partition"):
+        runner.partition(d, n_open, bool(p.sampled and FUSED_PACK and lv.more), zero,
+                         p.driver is _Driver.RUNNER and p.sampled, ws.rg_work if counted else None)
+    return ev, zero, counted
+
+
+def _python_plan_partition(cx: _TreeCtx, p: _Path, lv: _Level, packed) -> tuple:
+    """Python levels: ``tree_level_plan``, the next level's sample and active-item lists, the
+    counts' copy to the host and its event, the partition (sampled RF levels: the next level's
+    packed row state written on the way). Returns (event, the next level's zeroed histograms or
+    None)."""
+    C, Q, ws, st, params = cx.C, cx.Q, cx.ws, cx.st, cx.params
+    d, n_open, nxt = lv.d, lv.n_open, 1 - lv.cur
+    C.tree_level_plan(packed, n_open, d, params.max_depth, int(params.mode), p.build_all, ws.kexp,
+                      float(params.min_gain), Q.zbin, st.hot_row,
+                      st.n_nodes, st.stats, st.parent, st.left, st.right, st.feat, st.bin, st.leaf, st.gain,
+                      lv.open, lv.n_open_ptr, st.default_child, st.node_dense, *st.cs, st.counts[d],
+                      st.open[nxt], st.totals[nxt], st.node_slot, st.s2n, st.sub_dst, st.sub_par, st.sub_sib)
+    nxt_open = st.open[nxt][:2 * n_open]      # at most 2 n_open long, -1 padded (tree.h level_plan_reset)
+    if p.compact and lv.more:
+        cx.shards.sample_compact(C, nxt, cx.seed, cx.tree, nxt_open, int(Q.num_features), int(params.feat_k),
+                                 Q.fid_orig)
+    if p.sel_ids and lv.more:
+        if p.compact:
+            mask_n = cx.shards.compact_mask(nxt)
+        else:
+            mask_n = st.rf_mask[nxt]
+            C.tree_rf_sample(cx.seed, cx.tree, nxt_open, int(Q.num_features), int(params.feat_k), Q.fid_orig,
+                             st.rf_thr[nxt][:2 * n_open], mask_n, None)
+        groups = [p.item_groups[gi] for gi in p.sel_ids]
+        C.tree_hist_select_groups([[g.item_start, g.item_f0, g.item_meta, g.wave_order()] for g in groups], Q.nbins,
+                                  mask_n, [ws.item_list(gi, g)[0] for gi, g in zip(p.sel_ids, groups)],
+                                  st.counts[d, 4:].view(len(p.sel_ids), 8))
+    st.counts_host[d].copy_(st.counts[d], non_blocking=Q.device.type == "cuda")
+    ev = st.record_event(cx.stream)
+    with tracing.span("tree.partition"):
+        fuse = p.sampled and FUSED_PACK and lv.more
+        C.tree_partition_cols(ws.row_node, st.default_child, *st.cs, st.counts[d], Q.colptr, Q.csc_row, Q.csc_bin,
+                              st.node_dense, Q.dense if st.node_dense is not None else None, n_open, PARTITION_WPS,
+                              *((st.node_slot, ws.rowdig, ws.rowpack()) if fuse else (None, None, None)))
+    if p.dp or not lv.more:
+        return ev, None
+    return ev, torch.zeros((2 * n_open, Q.TB, 2), dtype=torch.int64, device=Q.device)
+
+
+def _read_tree(cx: _TreeCtx, p: _Path, deferred: bool):
+    """The end of every tree (a generator): one read of the node table, the arena (table +
+    exponents) in one D2H copy and one wait; ``deferred`` GBDT trees return a PendingTree whose
+    margin update reads the device node table (one launch with the runner)."""
+    st, ws, params = cx.st, cx.ws, cx.params
+    if p.driver is _Driver.PYTHON:         # (the runner's prologues write the exponents themselves)
+        st.kexp_slot.copy_(ws.kexp)
+    node_value = None
+    if deferred and params.mode == 0:
+        node_value = (p.runner, params) if p.runner is not None else leaf_values_device(st.stats, ws.kexp, params)
+    st.arena_host.copy_(st.arena, non_blocking=True)
+    cuda = cx.Q.device.type == "cuda"
+    done = torch.cuda.Event() if cuda else _Done()
+    if cuda:
+        done.record(cx.stream)
+
+    def finish() -> Tree:
+        done.synchronize()
+        return tree_from_host(cx.Q, params, st.host)
+
+    if node_value is not None:
+        return PendingTree(node_value, finish)
+    yield done
+    return finish()
+
+
 def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_index: int, g: torch.Tensor,
                       h: torch.Tensor, weight: Optional[torch.Tensor] = None, coll=None,
                       shards: Optional["FeatureShards"] = None, label: Optional[torch.Tensor] = None,
@@ -923,476 +1405,69 @@ def device_tree_steps(Q: Quantized, ws: Workspace, params: GrowParams, tree_inde
     counts, the finished node table) and returns the Tree (or PendingTree). :func:`drive` runs
     one tree; the forest driver (models/forest_batch.py) interleaves several on their own streams.
 
-    GBDT tree with the level loop on the device (same trees as grow_tree's host loop, bit for
-    bit). Per level: histogram passes -> sibling subtraction -> split search -> best split per
-    node -> ``tree_level_plan`` (one thread: apply the splits to the device node table, this
-    level's partition tables, the next level's open list / builds / subtraction triples) ->
-    partition. The host waits only for the plan's 16-byte counts (copied while the partition
-    runs) to size the next level's launches, and reads the node table once at the end.
-    Data parallel (``shards``): the built nodes' partial histograms are reduce-scattered by
-    feature shard and the per-shard best splits all-gathered, all stream-ordered on the device;
-    every rank plans the identical next level from the identical gathered splits.
+    One tree with the level loop on the device (same trees as grow_tree's host loop, bit for
+    bit), by the driver _resolve_tree picks. The generic loop, per level: feature sample ->
+    histogram passes -> sibling subtraction -> split search -> plan (the splits applied to the
+    device node table, this level's partition tables, the next level's open list / builds /
+    subtraction triples) -> partition. The host waits only for the plan's 16-byte counts (copied
+    while the partition runs) to size the next level's launches, and reads the node table once at
+    the end. Data parallel (``shards``): the built nodes' partial histograms are reduce-scattered
+    by feature shard and the per-shard best splits all-gathered (the CollStep yields), stream-
+    ordered on the device; every rank plans the identical next level from the gathered splits.
     ``deferred`` (GBDT): return a :class:`PendingTree` whose leaf values were computed on the
     device; the host table is built later (``on_first_wait`` of the next tree runs it while that
     tree's root level is on the GPU), so the GPU never idles on the host's tree build.
     ``margin`` (GBDT, with ``label`` and g = h = None): the round's gradients are computed here,
     fused into the tree's prologue when the native runner drives the levels."""
-    C = native.lib()
-    dev = Q.device
-    np_ = _choose_np(params, weight)
-    mode_rs = 0 if params.mode == 0 else 1
-    build_all = bool(params.feat_k)
-    sampled = build_all and np_ == 1
-    # RF levels >= 1: the next level's feature sample and its active-item lists are queued right
-    # after the plan, so the per-XCD item counts reach the host with the level's counts and each
-    # histogram pass launches one wave per active item (no grid of ~300K mostly idle wave slots)
-    presel = PRESELECT and sampled and dev.type == "cuda"
-    item_groups = (Q.groups + Q.hot_groups) if sampled else []
-    sel_ids = [gi for gi, grp in enumerate(item_groups) if grp.num_items] if presel else []
-    sel_args = None
-    st = getattr(ws, "_levels", None)
-    if st is None or st.max_depth != params.max_depth or st.n_sel != len(sel_ids):
-        st = ws._levels = LevelState(Q, params.max_depth, len(sel_ids))
-    # the native runner: RF levels and GBDT levels (any world size). A single process also fuses
-    # the GBDT prologue and the split + plan; under data parallelism the quantisation max is an
-    # all-reduce and the levels split around the reduce-scatter / all-gather
-    gbdt_native = NATIVE_LEVELS and dev.type == "cuda" and params.mode == 0 and weight is None and not build_all
-    # (the runner's level 0 completes the root's sums: at least one level)
-    runner = _level_runner(Q, ws, st, params, item_groups, sampled) \
-        if (NATIVE_LEVELS and dev.type == "cuda" and (sampled or gbdt_native) and params.max_depth >= 1) else None
-    # every step of this generator runs on the stream current now (the forest driver advances a
-    # lane inside that lane's stream context)
-    cur_stream = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-    seed = int(params.seed)
-    native_prologue = runner is not None and shards is None and coll is None
-    TB = Q.TB
+    inp = _TreeInput(g, h, label, weight, bootstrap, margin)
+    cx, p = _resolve_tree(Q, ws, params, tree_index, inp, coll, shards)
+    if p.driver is _Driver.CXX_GBDT:
+        _cxx_gbdt_tree(cx, p, inp, on_first_wait)
+        return (yield from _read_tree(cx, p, deferred))
     # the next level's zeroed histograms (at most 2 open nodes per open node) are queued before
     # the host waits for its counts, so the fill runs while the host sizes that level
-    pre_hist = None
-    # GBDT rounds on the row-group engine, in one process or data parallel: the level loop runs in
-    # the runner (RfLevels.gbdt_levels; data parallel: around the level's collectives, RCCL called
-    # by the runner or Python callbacks)
-    dp = shards is not None
-    rg_native = ws.rowgroups() if (runner is not None and (dp or native_prologue) and gbdt_native and
-                                   GBDT_CXX_LEVELS and np_ == 4 and margin is not None and g is None) else None
-    if rg_native is not None:
-        with tracing.span("tree.quant"):
-            root_zero = _gbdt_setup(Q, ws, st, params, runner, rg_native, shards, coll)
-            g, h = ws.gh()
-            # gradients + max |g|, |h| (data parallel: all-reduced by the runner) + arena image + the
-            # root histogram (data parallel: the root's send region) zeroed, then the quantisation
-            runner.prologue(margin, g, h, label, None, int(tree_index), False, 4, None, ws.totals, None, Q.row0,
-                            root_zero, st.arena_init_dev)
-    elif native_prologue:
-        # the root histogram is zeroed by the prologue's first launch
-        pre_hist = torch.empty((1, TB, 2), dtype=torch.int64, device=dev)
-        with tracing.span("tree.quant"):
-            # (the dense-block digit planes only feed the MFMA dense path, off with the row groups)
-            digp = ws.digp if (ws.digp is not None and not build_all and ws.rowgroups() is None) else None
-            if np_ == 4 and margin is not None and g is None:
-                # gradients + max |g|, |h| + arena image + root histogram zero, then quant: 2 launches
-                g, h = ws.gh()
-                runner.prologue(margin, g, h, label, None, int(tree_index), False, 4, None, ws.totals, digp,
-                                Q.row0, pre_hist, st.arena_init_dev)
-            else:
-                # arena image first: the quantisation adds the root totals into it
-                st.arena.copy_(st.arena_init, non_blocking=True)
-                if np_ == 4:
-                    C.tree_quant_max(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, Q.n_rows,
-                                     ws.maxabs, Q.row0)
-                    runner.prologue(None, g, h, label, weight, int(tree_index), bool(bootstrap), 4, ws.maxabs,
-                                    ws.totals, digp, Q.row0, pre_hist, None)
-                else:
-                    runner.prologue(None, g, h, label, weight, int(tree_index), bool(bootstrap), 1, None, ws.totals,
-                                    digp, Q.row0, pre_hist, None)
-    else:
-        if margin is not None and g is None:
-            g, h = ws.gh()
-            C.tree_logistic_grad(margin, label, weight, g, h)
-        ws.row_node.zero_()
-    with tracing.span("tree.quant"):
-        if native_prologue or rg_native is not None:
-            pass
-        elif np_ == 4:
-            C.tree_quant_max(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, Q.n_rows,
-                             ws.maxabs, Q.row0)
-            mx = coll.max(ws.maxabs) if coll is not None else ws.maxabs
-            C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 4, mx, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0, float(params.subsample), ws.keepbits(params))
-        else:
-            C.tree_quant(g, h, label, weight, seed, int(tree_index), bool(bootstrap), mode_rs, 1, None, ws.rowdig,
-                         ws.kexp, ws.totals, ws.digp, Q.row0)
-    # root: node 0, open list [0] with the exact totals (no host round trip); under data
-    # parallelism the totals are summed by the root level's reduce-scatter (LaneBufs.tot_bin)
-    if not native_prologue and rg_native is None:
-        st.arena.copy_(st.arena_init, non_blocking=True)
-        st.open[0][:1].zero_()
-    if shards is None and not native_prologue:
-        tot = coll.sum(ws.totals) if coll is not None else ws.totals
-        st.stats[0].copy_(tot)
-        st.totals[0][:1].copy_(tot[None])
-    # GBDT column sampling: the tree's and every level's stage thresholds, queued behind the prologue
-    col = ColumnSampler.of(Q, ws, params)
-    if col is not None:
-        if runner is not None:
-            runner.col_begin(int(tree_index))
-        else:
-            col.begin(C, seed, int(tree_index))
-    n_open, n_build = 1, 1
-    prev_hist = prev_row_of = None
-    ev = None
-    rg_counted = False
-    # RF under data parallelism: each level reduce-scatters only its sampled features' bins; level
-    # d + 1's sample and layout are computed right after level d's plan, so their shard sizes reach
-    # the host with the level's counts (one wait per level; the root's before the loop)
-    compact = shards is not None and build_all and 0 < params.feat_k < Q.num_features and \
-        (RF_COMPACT == "1" or (RF_COMPACT == "auto" and shards.S > 1))
-    if compact:
-        shards.sample_compact(C, 0, seed, int(tree_index), st.open[0][:1], int(Q.num_features), int(params.feat_k),
+    pre_hist = _runner_prologue(cx, p, inp) if p.driver is _Driver.RUNNER else _python_prologue(cx, p, inp)
+    if p.compact:
+        shards.sample_compact(cx.C, 0, cx.seed, cx.tree, cx.st.open[0][:1], int(Q.num_features), int(params.feat_k),
                               Q.fid_orig)
-        yield st.record_event(cur_stream)
-    generic_depth = params.max_depth
-    if rg_native is not None:
-        # level 0 is queued, the previous tree's host table is built while it runs (on_first_wait),
-        # then levels 1.. run with the host waits inside the runner: same launches and trees as the
-        # generic loop below
-        runner.gbdt_root(int(tree_index))
-        if on_first_wait is not None:
-            on_first_wait()
-            on_first_wait = None
-        shape = runner.gbdt_levels(int(tree_index))
-        for j in range(0, len(shape), 2):
-            LEVEL_STATS["levels"] += 1
-            LEVEL_STATS["built_nodes"] += shape[j + 1]
-            LEVEL_STATS["hist_bytes"] += shape[j + 1] * TB * 16
-        generic_depth = 0
-    for d in range(generic_depth):
-        cur = d % 2
+        yield cx.st.record_event(cx.stream)
+    prev, ev, counted = (None, None), None, False       # (the previous level's histograms and row map)
+    for d in range(params.max_depth):
         if d > 0:
             if on_first_wait is not None:
                 on_first_wait()
                 on_first_wait = None
             yield ev
-            cnt = st.counts_host[d - 1].tolist()
-            n_open, n_build = int(cnt[1]), int(cnt[2])
-            if n_open == 0:
-                break
-            if sel_ids:       # largest per-XCD active-item count of each sampled group
-                per_xcd = {gi: max(cnt[4 + 8 * j: 12 + 8 * j]) for j, gi in enumerate(sel_ids)}
-                for j, gi in enumerate(sel_ids):
-                    if per_xcd[gi]:           # (launch_hist: (npx + 3) / 4 x 8 workgroups of 4 waves)
-                        LEVEL_STATS["listed_passes"] += 1
-                        LEVEL_STATS["listed_active_items"] += sum(cnt[4 + 8 * j: 12 + 8 * j])
-                        LEVEL_STATS["listed_grid_waves"] += (per_xcd[gi] + 3) // 4 * 8 * 4
-        LEVEL_STATS["levels"] += 1
-        LEVEL_STATS["built_nodes"] += n_build
-        LEVEL_STATS["hist_bytes"] += n_build * TB * 16          # (g, h) int64 partials of the built nodes
-        open_d, totals_d = st.open[cur][:n_open], st.totals[cur][:n_open]
-        if d == 0 and native_prologue:
-            totals_d = st.stats[:1]             # (unread: the runner sums the prologue's root slots)
-        n_open_ptr = st.one if d == 0 else st.counts[d - 1, 1:2]
-        # RF: exact k-of-F feature sample per open node and the level's union mask (device)
-        feat_thr = feat_mask = None
-        if compact:
-            feat_thr, feat_mask, local_c, Bs_c = shards.compact_level(cur, n_open)
-        elif build_all and sel_ids and d > 0:
-            feat_thr, feat_mask = st.rf_thr[cur][:n_open], st.rf_mask[cur]      # (queued with the plan)
-        elif build_all:
-            feat_thr = torch.empty(n_open, dtype=torch.float64, device=dev)
-            feat_mask = torch.empty(Q.Fa, dtype=torch.uint8, device=dev)
-            C.tree_rf_sample(seed, int(tree_index), open_d, int(Q.num_features), int(params.feat_k), Q.fid_orig,
-                             feat_thr, feat_mask, None)
-        col_kw = {}
-        if col is not None and runner is not None:
-            runner.col_level(d, open_d, int(tree_index))       # (node stage queued; find() reads the tables)
-        elif col is not None:
-            feat_thr, col_kw = col.level_args(C, seed, int(tree_index), d, open_d)
-        split_boff = shards.boff if shards is not None else None
+        lv = _open_level(cx, p, d)
+        if lv is None:
+            break
+        smp = _level_sample(cx, p, lv)
         bufs = None
-        if shards is None:
-            if pre_hist is not None and pre_hist.shape[0] >= n_open:
-                cur_hist = hist_target = pre_hist[:n_open]
-            else:
-                cur_hist = hist_target = torch.zeros((n_open, TB, 2), dtype=torch.int64, device=dev)
-            pre_hist = None
-            h_boff, h_stride = Q.boff, TB
-        else:
-            # the built nodes' local partials go straight into this tree's rows of the batch's
-            # shard-major send buffer (LaneBufs); compact levels send only the sampled features'
-            # bins (FeatureShards.sample_compact)
-            subs = 0 if (build_all or d == 0) else n_build
-            bufs = yield CollStep("alloc", rows=n_build, Bs=Bs_c if compact else shards.Bs, n_open=n_open,
-                                  totals=ws.totals if d == 0 else None, sub_rows=subs)
-            hist_target = bufs.prepare(ws.totals if d == 0 else None)
-            if runner is not None:      # (the runner's kernels add the shard offsets themselves)
-                h_boff = local_c if compact else shards._local
-            else:
-                h_boff = shards.boff_batched(bufs.shard_bins, local_c if compact else None)
-            h_stride = bufs.Bs
-            if compact:
-                split_boff = local_c[shards.f0: shards.f0 + shards.Fa + 1]
+        if p.dp:
+            bufs = yield CollStep("alloc", rows=lv.n_build, Bs=smp.Bs, n_open=lv.n_open,
+                                  totals=ws.totals if d == 0 else None,
+                                  sub_rows=0 if (p.build_all or d == 0) else lv.n_build)
+        out = _hist_out(cx, p, lv, smp, bufs, pre_hist)
         with tracing.span("tree.hist"):
-            use_dense = Q.dense is not None and d <= DENSE_MAX_DEPTH and not build_all
-            slot8 = None
-            csc_slot8, csc_dig = None, ws.rowdig
-            rg = ws.rowgroups() if (not build_all and np_ == 4) else None
-            if d > 0:
-                # a single built node: the CSC passes run the root kernel on digit words zeroed
-                # outside it (no per-entry slot gather, no compaction; zero rows add nothing).
-                # Sampled RF levels with FUSED_PACK read the packed row state the previous level's
-                # partition wrote (no row pass here at all)
-                single = n_build == 1 and rg is None and not (sampled and FUSED_PACK)
-                if single and getattr(ws, "rowdig_masked", None) is None:
-                    ws.rowdig_masked = torch.empty_like(ws.rowdig)
-                if sampled and FUSED_PACK:
-                    pass
-                elif rg is None and sampled and not single:
-                    C.tree_slot_pack(ws.row_node, st.node_slot, n_build, ws.rowdig, ws.rowpack())
-                elif rg is None:        # (the row-group engine lists the built rows from row_node itself)
-                    C.tree_slot8(ws.row_node, st.node_slot, 0, n_build, ws.slot8, ws.rowdig if single else None,
-                                 ws.rowdig_masked if single else None)
-                slot8 = ws.slot8
-                csc_slot8, csc_dig = (None, ws.rowdig_masked) if single else (slot8, ws.rowdig)
-                s2n = st.s2n[:n_build]
-            else:
-                s2n = st.zero1
-            if shards is not None:      # slot k -> partial row k
-                s2n = ws.iota(n_build)
-            ct = pass_ct(np_, n_build)
-            launches = []
-            # (the CSC items are built on first use: the row-group engine never touches them)
-            sel_groups = None
-            if rg is not None:
-                shard_args = (shards.bin_lo, bufs.shard_bins) if shards is not None else (None, 0)
-                # per-workgroup partial tables summed by one reduction instead of every workgroup's
-                # atomics on the same bins (RgHistArgs part)
-                # (the listed levels have their own, smaller work table: RowGroups.list_work)
-                wtab = rg.work() if d == 0 else rg.list_work()
-                part = dict(part=ws.rg_part(rg, rg.list_work()), wg_first=rg.work_first() if d == 0 else
-                            rg.list_work_first()) if (RG_PARTIALS and dev.type == "cuda") else {}
-                if d == 0:
-                    C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, np_, None, None, None, 1, rg.gmode,
-                                   wtab, s2n, hist_target, h_stride, *shard_args, RG_DBG, **rg.em_args(), **part)
-                else:
-                    # one built node: every row's digit words zeroed outside it, for the
-                    # entry-major pass of the sparse groups (taken when the node is large)
-                    emdig = ws.rg_emdig() if (n_build == 1 and rg.erow is not None and qmod.RG_EM_MIN_FRAC <= 1.0) \
-                        else None
-                    C.tree_rg_list(ws.row_node, st.node_slot, None, Q.n_rows, n_build, ws.rg_work, ws.rg_start,
-                                   ws.rg_list, ws.rowdig, ws.rg_listdig, emdig, counted=rg_counted,
-                                   keepbits=ws.keepbits(params))
-                    C.tree_rg_hist(rg.ptr, rg.ent, rg.gbase, rg.gbin, ws.rowdig, np_, ws.rg_list, ws.rg_start,
-                                   ws.rg_listdig, n_build, rg.gmode, wtab, s2n, hist_target, h_stride,
-                                   *shard_args, RG_DBG, **(rg.em_args(emdig) if emdig is not None else {}), **part)
-                sel_groups, use_dense = [], False
-            if sel_groups is None:
-                sel_groups = Q.groups if use_dense else Q.groups + Q.hot_groups
-            if runner is not None and sampled:
-                pack = ws.rowpack() if (d > 0 and not single) else None
-                lists, cnts, npxs = [], [], []
-                for gi, grp in enumerate(sel_groups):
-                    lst = cnt = None
-                    npx = -1
-                    if grp.num_items and sel_ids and d > 0:
-                        j = sel_ids.index(gi)
-                        lst = ws.item_list(gi, grp)[0]
-                        cnt = st.counts[d - 1, 4 + 8 * j: 12 + 8 * j]
-                        npx = per_xcd[gi]
-                    elif grp.num_items and n_open <= LISTED_MAX_NODES:
-                        lst, cnt = ws.item_list(gi, grp)
-                    lists.append(lst)
-                    cnts.append(cnt)
-                    npxs.append(npx)
-                runner.hist(n_build, hist_target, h_boff, feat_mask, s2n, pack, lists, cnts, npxs,
-                            shards._shard_of if shards is not None else None,
-                            bufs.shard_bins if shards is not None else 0)
-                sel_groups = []
-            for gi, grp in enumerate(sel_groups):
-                if grp.num_items == 0:
-                    continue
-                if sampled:
-                    pack = ws.rowpack() if (d > 0 and not single) else None
-                    if sel_ids and d > 0:
-                        # preselected: exactly one wave per active item (the lists were built with
-                        # the previous level's plan)
-                        j = sel_ids.index(gi)
-                        lst = ws.item_list(gi, grp)[0]
-                        cnt = st.counts[d - 1, 4 + 8 * j: 12 + 8 * j]
-                        npx = per_xcd[gi]
-                    else:
-                        # the listed pass wins while few items are active (<= 2 open nodes: ~0.16
-                        # vs 0.19 ms at the root); with more, its fixed grid balances worse than a
-                        # wave per slot (profiles/r3s3/rf_probe_chunks.txt)
-                        lst, cnt = ws.item_list(gi, grp) if n_open <= LISTED_MAX_NODES else (None, None)
-                        npx = -1
-                    launches.append(functools.partial(
-                        C.tree_hist_sampled, grp.item_start, grp.item_end, grp.item_f0, grp.item_meta,
-                        grp.wave_order(), Q.h_row, Q.h_key, pack, csc_dig, h_boff, Q.nbins, s2n, hist_target, h_stride,
-                        grp.bt, ct, feat_mask, lst, cnt, RF_LDS, npx))
-                    continue
-                launches.append(functools.partial(
-                    C.tree_hist_build, grp.item_start, grp.item_end, grp.item_f0, grp.item_meta, grp.wave_order(),
-                    Q.h_row, Q.h_key, csc_slot8, csc_dig, h_boff, Q.nbins, s2n, hist_target, h_stride, grp.bt, ct,
-                    np_, feat_mask))
-            if use_dense:
-                for bt in (1, 2, 4):
-                    fg = C.tree_dense_fg(bt, ct if d > 0 else 1)
-                    gfid, gden = ws.dense_groups(bt, fg)
-                    if gfid.numel():
-                        rr = dense_range_rows(Q.n_rows, gfid.numel() // fg)
-                        launches.append(functools.partial(
-                            C.tree_hist_dense, Q.dense, ws.digp, ws.rowdig, None if d == 0 else ws.slot8_pad,
-                            gfid, gden, h_boff, Q.nbins, s2n, hist_target, h_stride, Q.n_rows, rr, bt, ct, np_))
-            ws.run_concurrent(launches)
-        row_of = None
-        if shards is not None:
+            rg = ws.rowgroups() if (not p.build_all and p.np_ == 4) else None
+            _level_hist(cx, p, lv, smp, out, bufs, rg, counted)
+        if p.dp:
             yield CollStep("rs")                  # (the batch's reduce-scatter, LevelBatcher.serve)
-            if d == 0:
-                tot = bufs.reduced_totals()
-                st.stats[0].copy_(tot)
-                totals_d.copy_(tot[None])
-            if build_all or d == 0:
-                # every open node built, slot k = open node k (tree.h level_plan): the reduced
-                # rows ARE the level's histograms (stride Bs, read in place by the split search)
-                cur_hist = bufs.mine()
-            else:
-                # the built rows stay where the collective wrote them and the subtraction fills
-                # rows after them: per open node its row (tree.h LevelRowsArgs), no copy
-                row_of = st.row_of[cur][:n_open]
-                C.tree_level_rows(st.s2n, st.sub_dst, st.sub_par, prev_row_of, n_build, bufs.row0, bufs.sub_base,
-                                  st.row_of[cur], st.dst_row, st.par_row, st.sib_row)
-                if LEVEL_CHECKS:
-                    n_sub = int((st.sub_dst[:n_build] >= 0).sum())
-                    assert n_build + n_sub == n_open, (d, n_build, n_sub, n_open)
-                cur_hist = bufs.out
-        # (single-process runner levels subtract inside the split search: split_plan prev_hist)
-        fused_sub = runner is not None and shards is None and d > 0 and not build_all
-        if d > 0 and not build_all and not fused_sub:
-            if shards is None:
-                C.tree_hist_subtract(prev_hist, cur_hist, st.sub_dst[:n_build], st.sub_par[:n_build],
-                                     st.sub_sib[:n_build], TB)
-            else:
-                C.tree_hist_subtract(prev_hist, cur_hist, st.dst_row[:n_build], st.par_row[:n_build],
-                                     st.sib_row[:n_build], bufs.Bs)
+        hist, row_of = _level_rows(cx, p, lv, out, bufs, prev)
         with tracing.span("tree.split"):
-            if runner is not None and shards is None:
-                packed = ws.split_cache.get(("out", n_open))
-                if packed is None:
-                    packed = ws.split_cache[("out", n_open)] = torch.empty((n_open, 5), dtype=torch.int64, device=dev)
-                # (split search, best split and level plan: 2 launches, below)
-            elif runner is not None:
-                runner.split(cur_hist, totals_d, split_boff, shards.nbins, shards.zbin, shards.fid_orig, open_d,
-                             feat_thr, int(tree_index), shards.f0, bufs.ag_in, row_of,
-                             _wide_features(shards.nbins, shards.Fa), d if col is not None else -1)
+            packed = _split_search(cx, p, lv, smp, hist, bufs, row_of)
+            if p.dp:
+                # [S, n_open, 5] (the batch's all-gather): the plan takes the best over shards per
+                # node (ties to the lowest shard = the lowest feature)
                 packed = yield CollStep("ag")
-            elif shards is None:
-                packed = _best_splits(C, cur_hist, totals_d, Q.boff, Q.nbins, Q.zbin, Q.fid_orig, open_d, ws.kexp,
-                                      params, feat_thr, tree_index, Q.Fa, 0, cache=ws.split_cache, **col_kw)
-            else:
-                _best_splits(C, cur_hist, totals_d, split_boff, shards.nbins, shards.zbin, shards.fid_orig,
-                             open_d, ws.kexp, params, feat_thr, tree_index, shards.Fa, shards.f0,
-                             cache=ws.split_cache, out=bufs.ag_in, row_of=row_of, **col_kw)
-                # [S, n_open, 5] (the batch's all-gather): tree_level_plan takes the best over
-                # shards per node (ties to the lowest shard = the lowest feature)
-                packed = yield CollStep("ag")
-        nxt = 1 - cur
-        if runner is not None:
-            more = d + 1 < params.max_depth
-            sample_next = more and (compact or bool(sel_ids))
-            if sample_next and compact:
-                thr_n, mask_n = shards.compact_thr(nxt, 2 * n_open), shards.compact_mask(nxt)
-                lay = (shards._fs_dev, Q.nbins, shards._local_c[nxt], shards._sizes[nxt], shards.sizes_host[nxt],
-                       shards.max_shard_features)
-            elif sample_next:
-                thr_n, mask_n, lay = st.rf_thr[nxt], st.rf_mask[nxt], (None,) * 5 + (0,)
-            else:
-                thr_n = mask_n = None
-                lay = (None,) * 5 + (0,)
-            if sel_ids and more:
-                if sel_args is None:
-                    sel_args = [ws.item_list(gi, grp)[0] if gi in sel_ids else None
-                                for gi, grp in enumerate(item_groups)]
-                sel = sel_args
-            else:
-                sel = []
-            if shards is None:
-                runner.split_plan(d, n_open, cur_hist, totals_d, Q.boff, feat_thr, int(tree_index), packed,
-                                  _wide_features(Q.nbins, Q.Fa), open_d, n_open_ptr,
-                                  st.open[nxt], st.totals[nxt], sample_next, thr_n, mask_n, sel,
-                                  prev_hist if fused_sub else None)
-            else:
-                runner.plan(d, n_open, packed, open_d, n_open_ptr, st.open[nxt], st.totals[nxt], int(tree_index),
-                            sample_next, thr_n, mask_n, *lay, sel)
-            ev = st.record_event(cur_stream)
-            zero = None
-            if shards is None and more and not build_all:
-                # the next level's histograms, zeroed by the partition kernel on the way
-                pre_hist = zero = torch.empty((2 * n_open, TB, 2), dtype=torch.int64, device=dev)
-            # the next level's row-list counts written by the partition's row pass (one pass less)
-            rg_counted = bool(more and rg is not None and PARTITION_COUNTS and C.tree_partition_counts_ok(Q.n_rows))
-            with tracing.span("tree.partition"):
-                runner.partition(d, n_open, bool(sampled and FUSED_PACK and more), zero, native_prologue and sampled,
-                                 ws.rg_work if rg_counted else None)
-            prev_hist = cur_hist
-            prev_row_of = row_of
-            continue
-        C.tree_level_plan(packed, n_open, d, params.max_depth, int(params.mode), build_all, ws.kexp,
-                          float(params.min_gain), Q.zbin, st.hot_row,
-                          st.n_nodes, st.stats, st.parent, st.left, st.right, st.feat, st.bin, st.leaf, st.gain,
-                          open_d, n_open_ptr, st.default_child, st.node_dense, *st.cs, st.counts[d],
-                          st.open[nxt], st.totals[nxt], st.node_slot, st.s2n, st.sub_dst, st.sub_par, st.sub_sib)
-        if compact and d + 1 < params.max_depth:
-            # level d + 1's open list is at most 2 n_open long, -1 padded (tree.h level_plan_reset)
-            shards.sample_compact(C, nxt, seed, int(tree_index), st.open[nxt][:2 * n_open], int(Q.num_features),
-                                  int(params.feat_k), Q.fid_orig)
-        if sel_ids and d + 1 < params.max_depth:
-            nxt_open = st.open[nxt][:2 * n_open]
-            if compact:
-                mask_n = shards.compact_mask(nxt)
-            else:
-                mask_n = st.rf_mask[nxt]
-                C.tree_rf_sample(seed, int(tree_index), nxt_open, int(Q.num_features), int(params.feat_k),
-                                 Q.fid_orig, st.rf_thr[nxt][:2 * n_open], mask_n, None)
-            if sel_args is None:
-                sel_args = ([[item_groups[gi].item_start, item_groups[gi].item_f0, item_groups[gi].item_meta,
-                              item_groups[gi].wave_order()] for gi in sel_ids],
-                            [ws.item_list(gi, item_groups[gi])[0] for gi in sel_ids])
-            C.tree_hist_select_groups(sel_args[0], Q.nbins, mask_n, sel_args[1],
-                                      st.counts[d, 4:].view(len(sel_ids), 8))
-        st.counts_host[d].copy_(st.counts[d], non_blocking=dev.type == "cuda")
-        ev = st.record_event(cur_stream)
-        with tracing.span("tree.partition"):
-            # (sampled RF levels: the next level's packed row state is written on the way)
-            fuse = sampled and FUSED_PACK and d + 1 < params.max_depth
-            C.tree_partition_cols(ws.row_node, st.default_child, *st.cs, st.counts[d], Q.colptr, Q.csc_row, Q.csc_bin,
-                                  st.node_dense, Q.dense if st.node_dense is not None else None, n_open, PARTITION_WPS,
-                                  *((st.node_slot, ws.rowdig, ws.rowpack()) if fuse else (None, None, None)))
-        if shards is None and d + 1 < params.max_depth:
-            pre_hist = torch.zeros((2 * n_open, TB, 2), dtype=torch.int64, device=dev)
-        prev_hist = cur_hist
-        prev_row_of = row_of
+        if p.runner is not None:
+            ev, pre_hist, counted = _runner_plan_partition(cx, p, lv, smp, hist, packed, prev[0], rg)
+        else:
+            ev, pre_hist = _python_plan_partition(cx, p, lv, packed)
+        prev = (hist, row_of)
     if on_first_wait is not None:          # (a one-level tree) the previous table first
         on_first_wait()
-    # one read of the node table per tree: the arena (table + exponents) in one D2H copy, one wait
-    if not native_prologue and rg_native is None:      # (the prologue's quantisation wrote them)
-        st.kexp_slot.copy_(ws.kexp)
-    node_value = None
-    if deferred and params.mode == 0:
-        # the margin update reads the device node table (one launch with the runner)
-        node_value = (runner, params) if runner is not None else leaf_values_device(st.stats, ws.kexp, params)
-    st.arena_host.copy_(st.arena, non_blocking=True)
-    done = torch.cuda.Event() if dev.type == "cuda" else _Done()
-    if dev.type == "cuda":
-        done.record(cur_stream)
-
-    def finish() -> Tree:
-        done.synchronize()
-        return tree_from_host(Q, params, st.host)
-
-    if node_value is not None:
-        return PendingTree(node_value, finish)
-    yield done
-    return finish()
+    return (yield from _read_tree(cx, p, deferred))
 
 
 class _Done:
