@@ -725,6 +725,7 @@ void register_lr_ops(pybind11::module& m);
 void register_sim_ops(pybind11::module& m);
 void register_nb_ops(pybind11::module& m);
 void register_mlr_ops(pybind11::module& m);
+void register_svc_ops(pybind11::module& m);
 void register_softprob_ops(pybind11::module& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -737,6 +738,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_sim_ops(m);
   register_nb_ops(m);
   register_mlr_ops(m);
+  register_svc_ops(m);
   register_softprob_ops(m);
   m.def("token_keys", &token_keys, "CountVectorizer fit: 64-bit token keys (count pass / key pass)");
   m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score",

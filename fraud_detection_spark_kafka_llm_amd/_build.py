@@ -330,6 +330,24 @@ def build_softprob_selftest(sanitize: bool = True, out: Path | None = None) -> P
     return out
 
 
+def build_svc_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
+    """``csrc/tests/svc_selftest.cpp`` + the linear SVC host twin (``svc_cpu.cpp``) as a standalone
+    executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_mlr_selftest``
+    (host code only, one translation unit)."""
+    hipcc = _hipcc()
+    out = out or (BUILD / ("svc_selftest_asan" if sanitize else "svc_selftest"))
+    out.parent.mkdir(parents=True, exist_ok=True)
+    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
+             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
+    if sanitize:
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
+    unity = out.parent / "svc_selftest_unity.cpp"
+    unity.write_text(f'#include "{CSRC / "svc_cpu.cpp"}"\n#include "{CSRC / "tests" / "svc_selftest.cpp"}"\n')
+    link = ["-fsanitize=address,undefined"] if sanitize else []
+    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
+    return out
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--force", action="store_true")
@@ -354,7 +372,11 @@ def main(argv=None) -> int:
                     help="build + run the ASan/UBSan self-test of the class-score tail of the featurizer's host twin")
     ap.add_argument("--softprob-selftest", action="store_true",
                     help="build + run the ASan/UBSan self-test of the multi-class boosting host twins")
+    ap.add_argument("--svc-selftest", action="store_true",
+                    help="build + run the ASan/UBSan self-test of the linear SVC host twin")
     args = ap.parse_args(argv)
+    if args.svc_selftest:
+        return subprocess.run([str(build_svc_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.softprob_selftest:
         return subprocess.run([str(build_softprob_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
     if args.cls_selftest:

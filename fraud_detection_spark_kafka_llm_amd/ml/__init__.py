@@ -1,8 +1,8 @@
 """Spark-ML-compatible API (pyspark.ml surface used by the reference)."""
 from .base import Estimator, Model, Param, Params, Pipeline, PipelineModel, Transformer
-from .classification import (DecisionTreeClassificationModel, DecisionTreeClassifier, LogisticRegression,
-                             LogisticRegressionModel, NaiveBayes, NaiveBayesModel, RandomForestClassificationModel,
-                             RandomForestClassifier)
+from .classification import (DecisionTreeClassificationModel, DecisionTreeClassifier, LinearSVC, LinearSVCModel,
+                             LogisticRegression, LogisticRegressionModel, NaiveBayes, NaiveBayesModel,
+                             RandomForestClassificationModel, RandomForestClassifier)
 from .feature import (IDF, CountVectorizer, CountVectorizerModel, HashingTF, IDFModel, NGram, StopWordsRemover,
                       Tokenizer)
 from .frame import Frame, Row, TextColumn, TokenColumn

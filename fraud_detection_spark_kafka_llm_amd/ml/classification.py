@@ -1,4 +1,4 @@
-"""Classifiers: LogisticRegression, DecisionTreeClassifier, RandomForestClassifier, NaiveBayes (+ models).
+"""Classifiers: LogisticRegression, LinearSVC, DecisionTreeClassifier, RandomForestClassifier, NaiveBayes (+ models).
 
 Models score through the native engine: either fused with the text featurizer
 (``ml.fused``; one gfx950 launch from raw bytes to scores) or over an existing feature column
@@ -753,3 +753,129 @@ class NaiveBayesModel(_NBParams, ClassificationModelBase):
     def _load_data(self, path, md) -> None:
         row = sf.read_data_parquet(path).to_pylist()[0]
         self._set_model(sf.decode_vector(row["pi"]), sf.decode_matrix(row["theta"]))
+
+
+# ============================================================================ linear SVC
+class _SVCParams(_PredictorParams):
+    _params = [Param("weightCol", "weight column", None, str, has_default=False),
+               Param("maxIter", "max iterations", 100, int),
+               Param("regParam", "regularization", 0.0, float),
+               Param("tol", "convergence tolerance", 1e-6, float),
+               Param("fitIntercept", "fit an intercept", True, bool),
+               Param("standardization", "standardize features", True, bool),
+               Param("threshold", "threshold applied to the margin (rawPrediction[1])", 0.0, float),
+               Param("aggregationDepth", "treeAggregate depth", 2, int),
+               Param("maxBlockSizeInMB", "block size", 0.0, float)]
+
+    _DEFAULT_ORDER = ("featuresCol", "labelCol", "predictionCol", "rawPredictionCol", "maxIter", "regParam", "tol",
+                      "fitIntercept", "standardization", "threshold", "aggregationDepth", "maxBlockSizeInMB")
+
+    @classmethod
+    def params(cls) -> list:
+        # Spark's LinearSVC is no probabilistic classifier: it has no probabilityCol
+        return [p for p in super().params() if p.name != "probabilityCol"]
+
+    def _default_hook(self) -> None:
+        d = self._defaultParamMap
+        self._defaultParamMap = {k: d[k] for k in self._DEFAULT_ORDER if k in d}
+
+
+@register("org.apache.spark.ml.classification.LinearSVC")
+class LinearSVC(_SVCParams, Estimator):
+    """Spark's ``LinearSVC``: hinge loss with an L2 penalty on labels in {0, 1}, fitted by
+    ``models/svm.py::train_linear_svc`` on the fused exact hinge pass. Data parallelism is through the
+    ambient process group, as for ``LogisticRegression``."""
+    _uid_prefix = "LinearSVC"
+
+    def _fit(self, frame: Frame) -> "LinearSVCModel":
+        from ..models.svm import train_linear_svc
+
+        w = frame.column(self.getWeightCol()) if self.isSet("weightCol") else None
+        coef, intercept, history = train_linear_svc(
+            frame.column(self.getFeaturesCol()), frame.column(self.getLabelCol()), weights=w,
+            max_iter=self.getMaxIter(), tol=self.getTol(), reg_param=self.getRegParam(),
+            fit_intercept=self.getFitIntercept(), standardization=self.getStandardization())
+        m = LinearSVCModel(coef, intercept, uid=self.uid)
+        m._paramMap.update(self._paramMap)
+        m.objectiveHistory = history
+        return m
+
+
+@register("org.apache.spark.ml.classification.LinearSVCModel")
+class LinearSVCModel(_SVCParams, ClassificationModelBase):
+    """One coefficient vector and one intercept. ``rawPrediction = [-m, m]`` with the margin
+    ``m = coefficients . x + intercept``, ``prediction = 1.0`` iff ``m > threshold``; ``transform``
+    adds no probability column, as Spark.
+
+    The serving glue (``FusedPipeline.predict``, the agent, the streaming engine) expects a triple
+    from ``postprocess``; its middle element is ``[sigma(-(m - threshold)), sigma(m - threshold)]``,
+    which those paths report as ``confidence``. That is a monotone squashing of the margin, not a
+    calibrated probability, and never a ``transform`` column: it is ``> 0.5`` exactly when the
+    prediction is 1."""
+    _uid_prefix = "LinearSVC"
+
+    def __init__(self, coefficients=None, intercept: float = 0.0, **kw):
+        super().__init__(**kw)
+        self._set_model(coefficients if coefficients is not None else [], intercept)
+        self.objectiveHistory: list = []
+
+    def _set_model(self, coefficients, intercept) -> None:
+        self._w = np.ascontiguousarray(coefficients, dtype=np.float64).reshape(-1)
+        self._b = float(intercept)
+        self._scorer = None
+
+    @property
+    def numFeatures(self) -> int:  # noqa: N802
+        return int(self._w.size)
+
+    @property
+    def coefficients(self) -> np.ndarray:
+        return self._w
+
+    @property
+    def intercept(self) -> float:
+        return self._b
+
+    def scorer(self) -> LinearScorer:
+        if self._scorer is None:
+            self._scorer = LinearScorer(self._w, self._b)
+        return self._scorer
+
+    def postprocess(self, raw: torch.Tensor):
+        m = raw[:, 0]
+        rp = torch.stack([-m, m], dim=1)
+        t = m - self.getThreshold()
+        squashed = 1.0 / (1.0 + torch.exp(-torch.stack([-t, t], dim=1)))
+        return rp, squashed, (m > self.getThreshold()).to(torch.float64)
+
+    def attach_outputs(self, frame: Frame, raw: torch.Tensor) -> Frame:
+        rp, _, pred = self.postprocess(raw)
+        if self.getRawPredictionCol():
+            frame = frame.withColumn(self.getRawPredictionCol(), rp)
+        return frame.withColumn(self.getPredictionCol(), pred)
+
+    def predictRaw(self, features) -> DenseVector:  # noqa: N802
+        from ..ops.sparse import score_csr
+
+        vc = VectorColumn.from_rows([features], size=self.numFeatures)
+        return DenseVector(self.postprocess(score_csr(vc, self.scorer()))[0][0].cpu().numpy())
+
+    def predictProbability(self, features) -> DenseVector:  # noqa: N802
+        raise AttributeError("LinearSVCModel has no probability (Spark's LinearSVC is not probabilistic)")
+
+    def contributions(self, features) -> VectorColumn:
+        """Every row stores its own entries ``w_f * x_f``, then the intercept at ``numFeatures``; a row
+        sums to the margin."""
+        vc = self._features_column(features)
+        if vc.size != self.numFeatures:
+            raise ValueError(f"features have size {vc.size}, model expects {self.numFeatures}")
+        return _linear_contributions(vc, self.scorer().weights(vc.device), self.intercept, self.numFeatures)
+
+    def _save_data(self, path) -> None:
+        sf.write_data_parquet(path, [sf.Field.vector("coefficients"), sf.Field.simple("intercept", "double")],
+                              [{"coefficients": sf.dense_vector(self._w), "intercept": self._b}])
+
+    def _load_data(self, path, md) -> None:
+        row = sf.read_data_parquet(path).to_pylist()[0]
+        self._set_model(sf.decode_vector(row["coefficients"]), float(row["intercept"]))
+        self.objectiveHistory = []

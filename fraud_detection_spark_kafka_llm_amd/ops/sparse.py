@@ -340,6 +340,99 @@ def mlr_eval(indptr, idx, val, XS: torch.Tensor, b: torch.Tensor, y: torch.Tenso
     return MlrBlock(out, F, C_, *rows)
 
 
+def svc_limits() -> dict:
+    """Structural constants of the linear SVC kernel: those of ``nb_limits`` it shares (``chunk_rows``,
+    ``table_bytes``, ``max_table_bytes``, ``k_max``, ``sum_bits``, wave and workgroup size), the slots
+    of the default and of the largest LDS table (``hot_slots``, ``max_hot_slots``), the loss cap
+    (``loss_cap = 2^loss_bits``) and the two halves of the flag word (``flag_clamped``,
+    ``flag_bad_input``)."""
+    return dict(native.lib().svc_limits())
+
+
+@dataclass
+class SvcBlock:
+    """The int64 block of one ``svc_eval``: ``Gq`` [F], ``gbq``, ``lossq``, ``nact``, the flag word,
+    and the per-row outputs when they were asked for."""
+    block: torch.Tensor
+    F: int
+    margin: Optional[torch.Tensor] = None
+    r: Optional[torch.Tensor] = None
+    loss_row: Optional[torch.Tensor] = None
+
+    @property
+    def Gq(self) -> torch.Tensor:
+        return self.block[:self.F]
+
+    @property
+    def gbq(self) -> int:
+        return int(self.block[self.F])
+
+    @property
+    def lossq(self) -> int:
+        return int(self.block[self.F + 1])
+
+    @property
+    def nact(self) -> int:
+        return int(self.block[self.F + 2])
+
+    @property
+    def flag(self) -> int:
+        return int(self.block[self.F + 3])
+
+    @property
+    def clamped(self) -> bool:
+        return bool(self.flag & 0xFFFFFFFF)
+
+    @property
+    def bad_input(self) -> bool:
+        return bool(self.flag >> 32)
+
+
+def svc_eval(indptr, idx, val, xs: torch.Tensor, b: float, y: torch.Tensor, w: Optional[torch.Tensor],
+             k: int, kl: int, hot_tables: tuple = (None, None), want_rows: bool = False, chunk_rows: int = 0,
+             check_extents: bool = True, threads: int = 0) -> SvcBlock:
+    """One evaluation of the linear SVC hinge objective on a CSR (``val`` fp32 or fp64) in one fused
+    pass: margins bitwise ``spmv(X, xs) + b``, the row terms of ``csrc/svc.h`` and the exact int64
+    sums ``Gq[f] = sum rint(x_if r_i 2^k)``, ``gbq = sum rint(r_i 2^k)``,
+    ``lossq = sum rint(w_i min(loss_i, 2048) 2^kl)`` and ``nact``, the rows with a non-zero residual.
+    ``(k, kl)`` come from ``mlr_scale_exponents``. The whole block is a pure function of the inputs
+    and equal bit for bit on the host and the device: ``hot_tables`` (``nb_hot_tables(..., 1)`` of the
+    features summed in LDS on the device; the host ignores it), ``chunk_rows`` and ``threads`` change
+    the speed only. The block stays on the CSR's device; nothing is read back here, the caller tests
+    the flags. Raises ``ValueError`` for arguments of the wrong shape, dtype or range."""
+    lim = svc_limits()
+    dev = indptr.device
+    if indptr.dtype != torch.int64 or idx.dtype != torch.int32 or val.dtype not in (torch.float32, torch.float64):
+        raise ValueError("svc_eval: the CSR is (indptr int64, idx int32, val float32 / float64)")
+    if indptr.dim() != 1 or indptr.numel() < 1 or idx.numel() != val.numel():
+        raise ValueError("svc_eval: indptr holds rows + 1 entries, idx / val one per entry")
+    n = indptr.numel() - 1
+    if xs.dim() != 1 or xs.numel() < 1 or xs.dtype != torch.float64:
+        raise ValueError("svc_eval: xs is a float64 vector [F]")
+    F = int(xs.numel())
+    if y.dtype != torch.float64 or y.numel() != n:
+        raise ValueError("svc_eval: labels are float64, one per row")
+    if w is not None and (w.dtype != torch.float64 or w.numel() != n):
+        raise ValueError("svc_eval: weights are float64, one per row")
+    if any(t.device != dev for t in (idx, val, xs, y) + (() if w is None else (w,))):
+        raise ValueError("svc_eval: every tensor lives on the CSR's device")
+    if not (0 <= int(k) <= lim["k_max"] and 0 <= int(kl) <= lim["k_max"]):
+        raise ValueError(f"svc_eval: scale exponents lie in 0 .. {lim['k_max']}")
+    if not 0 <= int(chunk_rows) <= (1 << 20):
+        raise ValueError("svc_eval: chunk_rows out of range")
+    slot_of, hot_feat = hot_tables if dev.type == "cuda" else (None, None)
+    if (slot_of is None) != (hot_feat is None):
+        raise ValueError("svc_eval: slot_of and hot_feat come together")
+    if hot_feat is not None and (hot_feat.numel() * 8 > lim["max_table_bytes"] or slot_of.numel() != F):
+        raise ValueError("svc_eval: the hot set exceeds the LDS table or does not cover the feature space")
+    out = torch.zeros(F + 4, dtype=torch.int64, device=dev)
+    rows = [torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None for _ in range(3)]
+    native.lib().svc_eval(indptr.contiguous(), idx.contiguous(), val.contiguous(), xs.contiguous(), float(b),
+                          y.contiguous(), None if w is None else w.contiguous(), int(k), int(kl), slot_of, hot_feat,
+                          out, rows[0], rows[1], rows[2], int(chunk_rows), bool(check_extents), threads)
+    return SvcBlock(out, F, *rows)
+
+
 def softprob_limits() -> dict:
     """Structural constants of the multi-class boosting kernels: ``max_classes``, workgroup size
     (``block``), ``wave`` and the hessian floor (``min_hess``)."""

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from .data import synth
-from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, LogisticRegression, NaiveBayes, NGram, Pipeline,
-                 PipelineModel, RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
+from .ml import (IDF, CountVectorizer, DecisionTreeClassifier, Frame, LinearSVC, LogisticRegression, NaiveBayes, NGram,
+                 Pipeline, PipelineModel, RandomForestClassifier, StopWordsRemover, TextColumn, Tokenizer)
 from .ml.evaluation import evaluate_all
 from .ml.xgboost import SparkXGBClassifier
 from .ops.sparse import term_presence_by_label
@@ -233,6 +233,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--no-plots", action="store_true")
     ap.add_argument("--ngram", type=int, default=1, help="insert an NGram(n) stage after the stop-word remover")
     ap.add_argument("--naive-bayes", action="store_true", help="also train Spark's multinomial NaiveBayes")
+    ap.add_argument("--linear-svc", action="store_true", help="also train Spark's LinearSVC (hinge loss)")
     ap.add_argument("--lr-label-col", default=None, metavar="COL",
                     help="also fit a multinomial LogisticRegression on the integer-coded column COL (classes 0 .. C - 1)")
     ap.add_argument("--xgb-label-col", default=None, metavar="COL",
@@ -256,6 +257,8 @@ def main(argv=None) -> dict:
         classifiers = make_classifiers(args.num_trees, args.max_depth, args.seed)
         if args.naive_bayes:
             classifiers["NaiveBayes"] = NaiveBayes(featuresCol="features", labelCol="labels")
+        if args.linear_svc:
+            classifiers["LinearSVC"] = LinearSVC(featuresCol="features", labelCol="labels", regParam=0.01)
         models = train_models(train_df, build_feature_pipeline(args.vocab_size, args.ngram), classifiers)
         results = {name: evaluate_model(m, {"Validation": val_df, "Test": test_df}) for name, m in models.items()}
         print("\nModel Evaluation Results:")
