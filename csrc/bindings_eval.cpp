@@ -1,28 +1,15 @@
 // pybind11 bindings of the validation-monitoring ops (registered from bindings.cpp via
 // register_eval_ops): HIP tensors launch the gfx950 kernels on the current stream, CPU tensors
 // run the host twins. Shapes are validated here, before any launch.
-#include <torch/extension.h>
-
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
+#define FDX_PREFIX "fdx.eval: "
+#include "bindings_util.h"
 
 #include "eval.h"
 #include "ops.h"
 
 namespace {
 
-using at::Tensor;
 using c10::optional;
-
-#define FDX_CHECK(cond, msg) TORCH_CHECK(cond, "fdx.eval: ", msg)
-
-void chk(const Tensor& t, const at::Device& dev, at::ScalarType st, const char* name) {
-  FDX_CHECK(t.device() == dev, std::string(name) + " on wrong device");
-  FDX_CHECK(t.is_contiguous(), std::string(name) + " must be contiguous");
-  FDX_CHECK(t.scalar_type() == st, std::string(name) + " has wrong dtype");
-}
-
-hipStream_t stream(const at::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
 
 // table: (feat, bin, left, right, leaf, stats, kexp) of the level loop's node table;
 // quant: (fid_orig, boff, thresholds) of the Quantized features

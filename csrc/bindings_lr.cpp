@@ -2,32 +2,19 @@
 // register_lr_ops): HIP tensors launch the gfx950 kernels on the current stream, CPU tensors run
 // the host twins. Shapes, dtypes and the 16-byte alignment the parameter passes load with are
 // validated here, before any launch.
-#include <torch/extension.h>
-
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
+#define FDX_PREFIX "fdx.lr: "
+#include "bindings_util.h"
 
 #include "lr.h"
 #include "ops.h"
 
 namespace {
 
-using at::Tensor;
 using c10::optional;
-
-#define FDX_CHECK(cond, msg) TORCH_CHECK(cond, "fdx.lr: ", msg)
-
-void chk(const Tensor& t, const at::Device& dev, at::ScalarType st, const char* name) {
-  FDX_CHECK(t.device() == dev, std::string(name) + " on wrong device");
-  FDX_CHECK(t.is_contiguous(), std::string(name) + " must be contiguous");
-  FDX_CHECK(t.scalar_type() == st, std::string(name) + " has wrong dtype");
-}
 
 void chk16(const Tensor& t, const char* name) {
   FDX_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, std::string(name) + " must be 16-byte aligned");
 }
-
-hipStream_t stream(const at::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
 
 // partials: [2, ceil(rows / rows_per_partial)] (sum w loss, sum r)
 void lr_forward(const Tensor& indptr, const Tensor& idx, const Tensor& val, const Tensor& xs, const Tensor& b,

@@ -2,10 +2,8 @@
 // register_sim_ops): HIP tensors launch the gfx950 kernels on the current stream, CPU tensors run
 // the host twins. Shapes, dtypes, k and the queries' lengths (they bound the LDS tables) are
 // validated here, before any launch.
-#include <torch/extension.h>
-
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
+#define FDX_PREFIX "fdx.sim: "
+#include "bindings_util.h"
 
 #include <algorithm>
 
@@ -13,23 +11,11 @@
 
 namespace {
 
-using at::Tensor;
-
-#define FDX_CHECK(cond, msg) TORCH_CHECK(cond, "fdx.sim: ", msg)
-
-void chk(const Tensor& t, const at::Device& dev, at::ScalarType st, const char* name) {
-  FDX_CHECK(t.device() == dev, std::string(name) + " on wrong device");
-  FDX_CHECK(t.is_contiguous(), std::string(name) + " must be contiguous");
-  FDX_CHECK(t.scalar_type() == st, std::string(name) + " has wrong dtype");
-}
-
 void chk_val(const Tensor& val, const at::Device& dev) {
   FDX_CHECK(val.device() == dev && val.is_contiguous() &&
                 (val.scalar_type() == at::kFloat || val.scalar_type() == at::kDouble),
             "val must be contiguous float32 / float64 on the CSR's device");
 }
-
-hipStream_t stream(const at::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
 
 // bytes of per-chunk candidates held at once; longer query batches run in several passes
 constexpr int64_t kCandBudget = int64_t(256) << 20;

@@ -2,24 +2,12 @@
 // register_softprob_ops): HIP tensors launch the gfx950 kernels on the current stream, CPU tensors
 // run the host twins. Shapes, dtypes, strides and the class count are validated here, before any
 // launch; class ids and tree features are validated by ops/sparse.py on the host arrays.
-#include <torch/extension.h>
-
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
+#define FDX_PREFIX "fdx.softprob: "
+#include "bindings_util.h"
 
 #include "softprob.h"
 
 namespace {
-
-using at::Tensor;
-
-#define FDX_CHECK(cond, msg) TORCH_CHECK(cond, "fdx.softprob: ", msg)
-
-void chk(const Tensor& t, const at::Device& dev, at::ScalarType st, const char* name) {
-  FDX_CHECK(t.device() == dev, std::string(name) + " on wrong device");
-  FDX_CHECK(t.is_contiguous(), std::string(name) + " must be contiguous");
-  FDX_CHECK(t.scalar_type() == st, std::string(name) + " has wrong dtype");
-}
 
 void check_classes(int64_t C) {
   if (C < 2 || C > fdx::kSoftprobMaxClasses)

@@ -1,26 +1,16 @@
 // pybind11 bindings of the tree engine (registered from bindings.cpp via register_tree_ops).
-#include <torch/extension.h>
+#define FDX_PREFIX "fdx.tree: "
+#include "bindings_util.h"
 
 #include <cstdlib>
-#include <c10/hip/HIPGuard.h>
-#include <c10/hip/HIPStream.h>
 
 #include "ops.h"
 #include "tree.h"
 
 namespace {
 
-using at::Tensor;
 using c10::optional;
 using c10::nullopt;
-
-#define FDX_CHECK(cond, msg) TORCH_CHECK(cond, "fdx.tree: ", msg)
-
-void chk(const Tensor& t, const at::Device& dev, at::ScalarType st, const char* name) {
-  FDX_CHECK(t.device() == dev, std::string(name) + " on wrong device");
-  FDX_CHECK(t.is_contiguous(), std::string(name) + " must be contiguous");
-  FDX_CHECK(t.scalar_type() == st, std::string(name) + " has wrong dtype");
-}
 
 // t's storage extends at least `extra` elements past the end of t (views into padded buffers)
 bool readable_tail(const Tensor& t, int64_t extra) {
@@ -30,8 +20,6 @@ bool readable_tail(const Tensor& t, int64_t extra) {
 
 template <class T>
 const T* opt(const optional<Tensor>& t) { return (t && t->defined()) ? t->data_ptr<T>() : nullptr; }
-
-hipStream_t stream(const at::Device& d) { return c10::hip::getCurrentHIPStream(d.index()).stream(); }
 
 fdx::QuantArgs quant_args(const optional<Tensor>& g, const optional<Tensor>& h, const optional<Tensor>& label,
                            const optional<Tensor>& weight, int64_t seed, int64_t tree, bool bootstrap, int64_t mode,

@@ -22,11 +22,6 @@
 
 namespace fdx {
 
-constexpr double kMlrLossCap = 2048.0;             // a row's loss counts at most this much
-constexpr int kMlrLossBits = 11;                   // kMlrLossCap = 2^kMlrLossBits
-constexpr int64_t kMlrFlagClamped = 1;             // low half of the flag word
-constexpr int64_t kMlrFlagBadInput = int64_t(1) << 32;  // high half of the flag word
-
 FDX_HD bool mlr_weight_ok(double w) { return w >= 0.0 && w <= 1.79769313486231570815e308; }
 FDX_HD bool mlr_value_ok(double x) { return x >= -1.79769313486231570815e308 && x <= 1.79769313486231570815e308; }
 
@@ -58,24 +53,17 @@ FDX_HD double mlr_row_terms(const double (&m)[C], int y, double w, double (&r)[C
 }
 
 // ---------------------------------------------------------------- descriptor
-template <class V>
-struct MlrArgs {
-  const int64_t* indptr;     // [rows + 1]
-  const int32_t* idx;
-  const V* val;
+// comes first in MlrArgs: the kernel reads the coefficients with the CSR's pointers in one
+// argument load, which keeps its scalar registers where they were before the parts were shared
+struct MlrCoef {
   const double* XS;          // [F, num_classes] scaled coefficients, feature-major
   const double* b;           // [num_classes]
-  const double* labels;      // [rows]
-  const double* weights;     // [rows] or nullptr (1.0)
-  int64_t rows;
-  int32_t F;
+};
+
+template <class V>
+struct MlrArgs : MlrCoef, CsrRows<V>, HotSet {
   int num_classes;           // 2 .. kNbMaxClasses
   int k, kl;                 // scale exponents of the gradient terms and of the loss
-  // device only: the hot set (no hot set: hot_slots = 0)
-  const uint16_t* slot_of;   // [F] slot of a hot feature, >= hot_slots otherwise
-  const int32_t* hot_feat;   // [hot_slots] feature of a slot
-  int hot_slots;             // num_classes * hot_slots * 8 <= kNbMaxTableBytes
-  int chunk_rows;            // rows of a workgroup
   // sums, zeroed by the caller
   int64_t* Gq;               // [F, num_classes]
   int64_t* gbq;              // [num_classes]

@@ -1,14 +1,10 @@
-// Host twin of the multinomial logistic regression kernel (contract in mlr.h). Every thread owns a
-// range of rows and a private int64 block, and the blocks are merged: the sums are integers, so the
-// thread count does not change a bit. Margins are summed in nb_score's order (64 lane-strided
-// partials, halving adds, then + b_c); the row terms are mlr_row_terms, as on the device.
-#include <algorithm>
-#include <atomic>
+// Host twin of the multinomial logistic regression kernel (contract in mlr.h): its row body on the
+// host pass of fixedpoint.h (private blocks, merged: the thread count does not change a bit).
+// Margins are summed in nb_score's order (64 lane-strided partials, halving adds, then + b_c); the
+// row terms are mlr_row_terms, as on the device.
 #include <stdexcept>
-#include <vector>
 
 #include "mlr.h"
-#include "parallel_for.h"
 
 namespace fdx {
 
@@ -62,41 +58,13 @@ int64_t mlr_rows(const MlrArgs<V>& a, int64_t lo, int64_t hi, uint64_t* G, uint6
 
 template <class V, int C>
 void mlr_eval_c(const MlrArgs<V>& a, int threads) {
-  const int64_t width = (int64_t)C * a.F;
-  int T = threads <= 0 ? HostPool::get().size() : threads;
-  T = (int)std::max<int64_t>(1, std::min<int64_t>(T, a.rows / 256));
-  // thread 0 adds into the outputs themselves
-  std::vector<std::vector<uint64_t>> priv(T > 1 ? T - 1 : 0);
-  std::atomic<int64_t> flags{0};
-  const int64_t per = (a.rows + T - 1) / T;
-  parallel_for(T, T, 1, [&](int64_t lo, int64_t hi) {
-    for (int64_t t = lo; t < hi; ++t) {
-      uint64_t *G, *gb, *lossq;
-      if (t == 0) {
-        G = reinterpret_cast<uint64_t*>(a.Gq);
-        gb = reinterpret_cast<uint64_t*>(a.gbq);
-        lossq = reinterpret_cast<uint64_t*>(a.lossq);
-      } else {
-        priv[t - 1].assign((size_t)width + C + 1, 0);
-        G = priv[t - 1].data();
-        gb = G + width;
-        lossq = gb + C;
-      }
-      const int64_t f = mlr_rows<V, C>(a, std::min(a.rows, t * per), std::min(a.rows, (t + 1) * per), G, gb, lossq);
-      if (f) flags.fetch_or(f, std::memory_order_relaxed);
-    }
-  });
-  uint64_t* out = reinterpret_cast<uint64_t*>(a.Gq);
-  if (T > 1)
-    parallel_for(width, threads, 1 << 14, [&](int64_t lo, int64_t hi) {
-      for (const auto& p : priv)
-        for (int64_t i = lo; i < hi; ++i) out[i] += p[i];
-    });
-  for (const auto& p : priv) {
-    for (int c = 0; c < C; ++c) reinterpret_cast<uint64_t*>(a.gbq)[c] += p[width + c];
-    *reinterpret_cast<uint64_t*>(a.lossq) += p[width + C];
-  }
-  *a.flag |= flags.load();
+  uint64_t tail[C + 1] = {};                       // gbq [C] | lossq
+  *a.flag |= fx_host_pass(a.rows, threads, reinterpret_cast<uint64_t*>(a.Gq), (int64_t)C * a.F, tail, C + 1,
+                          [&](int64_t lo, int64_t hi, uint64_t* G, uint64_t* sums) {
+                            return mlr_rows<V, C>(a, lo, hi, G, sums, sums + C);
+                          });
+  for (int c = 0; c < C; ++c) reinterpret_cast<uint64_t*>(a.gbq)[c] += tail[c];
+  *reinterpret_cast<uint64_t*>(a.lossq) += tail[C];
 }
 
 }  // namespace

@@ -6,12 +6,8 @@
 // registers (C is a template parameter), sums them with the xor butterfly as nb_score does, and
 // every lane then holds the row's C margins and computes the row terms (uniform over the wave).
 // It walks the same entries again (they are in L1 / L2) and adds the C terms rint(x r_c 2^k) of an
-// entry: a feature of the hot set (slot_of[f] < hot_slots) adds into the workgroup's int64 LDS
-// table [H][C] with a 64-bit LDS atomic, every other entry goes straight to a global integer
-// atomic; zero terms are skipped. The table's non-zero slots are flushed with 64-bit integer global
-// atomics when the chunk is done. The intercept sums and the loss are summed per wave in registers,
-// then in LDS, and leave the workgroup as C + 1 global atomics. Integer adds commute, so the hot
-// set, the chunk size and the grid change the speed only.
+// entry into the feature-major table [H][C] or Gq (the fixed-point row pass of fixedpoint.h); zero
+// terms are skipped. The intercept sums and the loss are the scalar sums: C + 1 global atomics.
 #include <stdexcept>
 
 #include "mlr.h"
@@ -22,27 +18,19 @@ namespace fdx {
 
 namespace {
 
-using u64 = unsigned long long;
-
-__device__ __forceinline__ double mlr_wave_sum(double v) {
-#pragma unroll
-  for (int o = kNbWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kNbWave);
-  return v;
-}
+using u64 = fx_u64;
 
 template <class V, int C>
 __global__ __launch_bounds__(kNbBlock) void mlr_eval_kernel(MlrArgs<V> a) {
   extern __shared__ u64 table[];                 // [hot_slots][C]
   __shared__ u64 sums_s[kNbMaxClasses + 1];      // intercept sums, then the loss
   const int tid = threadIdx.x, lane = tid & (kNbWave - 1), wave = tid / kNbWave;
-  const int H = a.hot_slots;
-  const int slots = C * H;
-  for (int i = tid; i < slots; i += kNbBlock) table[i] = 0;
+  fx_table_zero(table, C * a.hot_slots);
   if (tid <= C) sums_s[tid] = 0;
   __syncthreads();
 
-  const int64_t r0 = (int64_t)blockIdx.x * a.chunk_rows;
-  const int64_t r1 = r0 + a.chunk_rows < a.rows ? r0 + a.chunk_rows : a.rows;
+  int64_t r0, r1;
+  fx_chunk(a, a.rows, r0, r1);
   double bias[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) bias[c] = a.b[c];
@@ -69,7 +57,7 @@ __global__ __launch_bounds__(kNbBlock) void mlr_eval_kernel(MlrArgs<V> a) {
       for (int c = 0; c < C; ++c) m[c] += x * xs[c];
     }
 #pragma unroll
-    for (int c = 0; c < C; ++c) m[c] = mlr_wave_sum(m[c]) + bias[c];
+    for (int c = 0; c < C; ++c) m[c] = fx_wave_sum(m[c]) + bias[c];
     bad_row = __any(bad_row);
     double res[C];
     double loss = 0.0;
@@ -100,8 +88,7 @@ __global__ __launch_bounds__(kNbBlock) void mlr_eval_kernel(MlrArgs<V> a) {
     for (int64_t j = s + lane; j < e; j += kNbWave) {
       const int32_t f = a.idx[j];
       const double x = (double)a.val[j];
-      const int slot = H ? (int)a.slot_of[f] : (int)kNbCold;
-      u64* const dst = slot < H ? table + slot * C : G + (int64_t)f * C;
+      u64* const dst = fx_dst<C>(a, table, G, f);
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const u64 q = (u64)nb_quant(x * res[c], a.k);
@@ -111,32 +98,20 @@ __global__ __launch_bounds__(kNbBlock) void mlr_eval_kernel(MlrArgs<V> a) {
   }
   if (lane == 0) {
 #pragma unroll
-    for (int c = 0; c < C; ++c)
-      if (gb[c]) atomicAdd(&sums_s[c], gb[c]);
-    if (lossq) atomicAdd(&sums_s[C], lossq);
+    for (int c = 0; c < C; ++c) fx_sum_to_lds(&sums_s[c], gb[c]);
+    fx_sum_to_lds(&sums_s[C], lossq);
   }
-  // every writer stores the same value into its half of the flag word
-  if (clamped_any) reinterpret_cast<int32_t*>(a.flag)[0] = 1;
-  if (bad) reinterpret_cast<int32_t*>(a.flag)[1] = 1;
+  fx_flag(a.flag, clamped_any, bad);
   __syncthreads();
-  for (int i = tid; i < slots; i += kNbBlock) {
-    const u64 v = table[i];
-    if (v == 0) continue;
-    const int slot = i / C;
-    const int32_t f = a.hot_feat[slot];
-    if ((uint32_t)f < (uint32_t)a.F) atomicAdd(G + (int64_t)f * C + (i - slot * C), v);
-  }
-  if (tid <= C && sums_s[tid]) {
-    // gbq [C] and lossq [1] are adjacent in the block only by the caller's choice: address each
-    atomicAdd(reinterpret_cast<u64*>(tid < C ? a.gbq + tid : a.lossq), sums_s[tid]);
-  }
+  fx_flush<C>(a, table, G, a.F);
+  // gbq [C] and lossq [1] are adjacent in the block only by the caller's choice: address each
+  if (tid <= C) fx_sum_to_global(tid < C ? a.gbq + tid : a.lossq, sums_s[tid]);
 }
 
 template <class V, int C>
 void launch_c(const MlrArgs<V>& a, hipStream_t stream) {
-  const size_t lds = (size_t)C * a.hot_slots * sizeof(u64);
-  const unsigned grid = (unsigned)nb_chunks(a.rows, a.chunk_rows);
-  hipLaunchKernelGGL((mlr_eval_kernel<V, C>), dim3(grid), dim3(kNbBlock), lds, stream, a);
+  const FxLaunch l = fx_launch("mlr_eval", C, 2, a, a.rows);
+  hipLaunchKernelGGL((mlr_eval_kernel<V, C>), dim3(l.grid), dim3(kNbBlock), l.lds, stream, a);
 }
 
 }  // namespace
@@ -144,9 +119,6 @@ void launch_c(const MlrArgs<V>& a, hipStream_t stream) {
 template <class V>
 void launch_mlr_eval(const MlrArgs<V>& a, hipStream_t stream) {
   if (a.rows <= 0) return;
-  if (a.num_classes < 2 || a.num_classes > kNbMaxClasses || a.chunk_rows < 1 || a.hot_slots < 0 ||
-      (int64_t)a.num_classes * a.hot_slots * 8 > kNbMaxTableBytes)
-    throw std::runtime_error("fdx mlr_eval: classes, chunk or hot set out of range");
   switch (a.num_classes) {
     case 2: launch_c<V, 2>(a, stream); break;
     case 3: launch_c<V, 3>(a, stream); break;
@@ -154,7 +126,8 @@ void launch_mlr_eval(const MlrArgs<V>& a, hipStream_t stream) {
     case 5: launch_c<V, 5>(a, stream); break;
     case 6: launch_c<V, 6>(a, stream); break;
     case 7: launch_c<V, 7>(a, stream); break;
-    default: launch_c<V, 8>(a, stream); break;
+    case 8: launch_c<V, 8>(a, stream); break;
+    default: throw std::runtime_error("fdx mlr_eval: classes out of range");
   }
 }
 template void launch_mlr_eval<float>(const MlrArgs<float>&, hipStream_t);

@@ -13,27 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-#include "common.h"
+#include "fixedpoint.h"
 
 #pragma clang fp contract(off)
 
 namespace fdx {
-
-constexpr int kNbWave = 64;
-constexpr int kNbBlock = 256;                      // lanes of a workgroup of nb_sums / nb_score
-constexpr int kNbWaves = kNbBlock / kNbWave;
-constexpr int kNbMaxClasses = kMaxClasses;
-constexpr int kNbChunkRows = 1024;                 // default rows of a workgroup of nb_sums
-constexpr int64_t kNbMaxChunkRows = 1 << 20;
-constexpr int kNbTableBytes = 32 * 1024;           // default LDS table of the hot features [C][H] int64 (swept)
-constexpr int kNbMaxTableBytes = 63 * 1024;        // with the 128 B of class sums a workgroup stays within 64 KiB
-constexpr int kNbKMax = 40;                        // largest scale exponent
-constexpr int kNbSumBits = 61;                     // |S| < 2^61
-constexpr int kNbPrefixRows = 65536;               // rows whose document frequencies choose the hot set
-constexpr uint16_t kNbCold = 0xFFFF;               // slot_of value of a feature outside the hot set
-
-// slots per class of an LDS table of `bytes`
-constexpr int nb_hot_slots(int num_classes, int bytes = kNbTableBytes) { return bytes / (8 * num_classes); }
 
 // q = rint(t 2^k) as int64, ties to even; the scaling by a power of two is exact
 FDX_HD int64_t nb_quant(double t, int k) { return (int64_t)rint(ldexp(t, k)); }
@@ -52,33 +36,12 @@ FDX_HD bool nb_value_ok(double x, bool bernoulli) {
   return bernoulli ? (x == 0.0 || x == 1.0) : (x >= 0.0 && x <= 1.79769313486231570815e308);
 }
 
-// host side of the 64-lane sum (lane 0 of the xor butterfly)
-inline double nb_butterfly_host(double* p) {
-  for (int o = kNbWave / 2; o > 0; o >>= 1)
-    for (int l = 0; l < o; ++l) p[l] = p[l] + p[l + o];
-  return p[0];
-}
-
-inline int64_t nb_chunks(int64_t rows, int64_t chunk_rows) { return (rows + chunk_rows - 1) / chunk_rows; }
-
 // ---------------------------------------------------------------- descriptors
 template <class V>
-struct NbSumArgs {
-  const int64_t* indptr;     // [rows + 1]
-  const int32_t* idx;
-  const V* val;
-  const double* labels;      // [rows]
-  const double* weights;     // [rows] or nullptr (1.0)
-  int64_t rows;
-  int32_t F;
+struct NbSumArgs : CsrRows<V>, HotSet {
   int num_classes;           // 2 .. kNbMaxClasses
   int k, kw;                 // scale exponents of the terms and of the weights
   bool bernoulli;
-  // device only: the hot set (no hot set: hot_slots = 0)
-  const uint16_t* slot_of;   // [F] slot of a hot feature, >= hot_slots otherwise
-  const int32_t* hot_feat;   // [hot_slots] feature of a slot
-  int hot_slots;             // num_classes * hot_slots * 8 <= kNbMaxTableBytes
-  int chunk_rows;            // rows of a workgroup
   // outputs, zeroed by the caller
   int64_t* S;                // [num_classes, F]
   int64_t* Wq;               // [num_classes]

@@ -1,12 +1,7 @@
 // Naive Bayes kernels for gfx950 (contracts in nb.h).
 //
-// nb_sums: a workgroup owns a contiguous chunk of rows, a wave one row at a time; entries are read
-// lane-strided and coalesced as in spmv_kernel. A feature of the hot set (slot_of[f] < hot_slots,
-// a 2-byte table that stays in L2) adds into the workgroup's int64 LDS table [C][H] with a 64-bit
-// LDS atomic; the table's non-zero slots are flushed with 64-bit integer global atomics when the
-// chunk is done. Every other entry goes straight to a global integer atomic. A token that occurs
-// in every row therefore costs one global atomic per workgroup and class instead of one per row.
-// Integer adds commute, so the hot set, the chunk size and the grid change the speed only.
+// nb_sums: the fixed-point row pass of fixedpoint.h with a class-major table [C][H]: a row adds to
+// its own class only, one walk over its entries.
 //
 // nb_score: a wave per row; one gather of W[f][0 .. C) brings every class of an entry, the C
 // partials of a lane stay in registers (C is a template parameter).
@@ -20,13 +15,7 @@ namespace fdx {
 
 namespace {
 
-using u64 = unsigned long long;
-
-__device__ __forceinline__ double nb_wave_sum(double v) {
-#pragma unroll
-  for (int o = kNbWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kNbWave);
-  return v;
-}
+using u64 = fx_u64;
 
 template <class V>
 __global__ __launch_bounds__(kNbBlock) void nb_sums_kernel(NbSumArgs<V> a) {
@@ -34,13 +23,12 @@ __global__ __launch_bounds__(kNbBlock) void nb_sums_kernel(NbSumArgs<V> a) {
   __shared__ u64 wq_s[kNbMaxClasses], cnt_s[kNbMaxClasses];
   const int tid = threadIdx.x, lane = tid & (kNbWave - 1), wave = tid / kNbWave;
   const int C = a.num_classes, H = a.hot_slots;
-  const int slots = C * H;
-  for (int i = tid; i < slots; i += kNbBlock) table[i] = 0;
+  fx_table_zero(table, C * H);
   if (tid < kNbMaxClasses) { wq_s[tid] = 0; cnt_s[tid] = 0; }
   __syncthreads();
 
-  const int64_t r0 = (int64_t)blockIdx.x * a.chunk_rows;
-  const int64_t r1 = r0 + a.chunk_rows < a.rows ? r0 + a.chunk_rows : a.rows;
+  int64_t r0, r1;
+  fx_chunk(a, a.rows, r0, r1);
   // per-wave sums of the weights and the rows of each class (the class is uniform over a wave)
   u64 wq[kNbMaxClasses], cnt[kNbMaxClasses];
 #pragma unroll
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(kNbBlock) void nb_sums_kernel(NbSumArgs<V> a) {
       if ((uint32_t)f >= (uint32_t)a.F || !nb_value_ok(x, a.bernoulli)) { bad = true; continue; }
       const u64 q = (u64)nb_quant(w * x, a.k);
       if (q == 0) continue;
-      const int slot = H ? (int)a.slot_of[f] : (int)kNbCold;
+      const int slot = fx_slot(a, f);             // two atomics: a selected pointer would make one flat atomic
       if (slot < H) atomicAdd(&t_row[slot], q);
       else atomicAdd(&g_row[f], q);
     }
@@ -77,13 +65,7 @@ __global__ __launch_bounds__(kNbBlock) void nb_sums_kernel(NbSumArgs<V> a) {
   }
   if (bad) *a.flag = 1;                          // every writer stores the same value
   __syncthreads();
-  for (int i = tid; i < slots; i += kNbBlock) {
-    const u64 v = table[i];
-    if (v == 0) continue;
-    const int c = i / H;
-    const int32_t f = a.hot_feat[i - c * H];
-    if ((uint32_t)f < (uint32_t)a.F) atomicAdd(reinterpret_cast<u64*>(a.S) + (int64_t)c * a.F + f, v);
-  }
+  fx_flush_rows(a, table, reinterpret_cast<u64*>(a.S), a.F, C);
   if (tid < C && cnt_s[tid]) {
     atomicAdd(reinterpret_cast<u64*>(a.Wq) + tid, wq_s[tid]);
     atomicAdd(reinterpret_cast<u64*>(a.cnt) + tid, cnt_s[tid]);
@@ -108,7 +90,7 @@ __global__ __launch_bounds__(kNbBlock) void nb_score_kernel(NbScoreArgs<V> a) {
     for (int c = 0; c < C; ++c) part[c] += x * w[c];
   }
 #pragma unroll
-  for (int c = 0; c < C; ++c) part[c] = nb_wave_sum(part[c]);
+  for (int c = 0; c < C; ++c) part[c] = fx_wave_sum(part[c]);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < C; ++c) a.out[r * C + c] = part[c] + a.b[c];
@@ -126,12 +108,8 @@ void launch_score_c(const NbScoreArgs<V>& a, hipStream_t stream) {
 template <class V>
 void launch_nb_sums(const NbSumArgs<V>& a, hipStream_t stream) {
   if (a.rows <= 0) return;
-  if (a.num_classes < 2 || a.num_classes > kNbMaxClasses || a.chunk_rows < 1 || a.hot_slots < 0 ||
-      (int64_t)a.num_classes * a.hot_slots * 8 > kNbMaxTableBytes)
-    throw std::runtime_error("fdx nb_sums: classes, chunk or hot set out of range");
-  const size_t lds = (size_t)a.num_classes * a.hot_slots * sizeof(u64);
-  const unsigned grid = (unsigned)nb_chunks(a.rows, a.chunk_rows);
-  hipLaunchKernelGGL(nb_sums_kernel<V>, dim3(grid), dim3(kNbBlock), lds, stream, a);
+  const FxLaunch l = fx_launch("nb_sums", a.num_classes, 2, a, a.rows);
+  hipLaunchKernelGGL(nb_sums_kernel<V>, dim3(l.grid), dim3(kNbBlock), l.lds, stream, a);
 }
 template void launch_nb_sums<float>(const NbSumArgs<float>&, hipStream_t);
 template void launch_nb_sums<double>(const NbSumArgs<double>&, hipStream_t);

@@ -12,7 +12,7 @@
 // Every term is exactly rounded fp64 arithmetic (no exp, no log) and the sums are integers, so the
 // whole block [Gq (F) | gbq | lossq | nact | flag], lossq included, is a pure function of the inputs:
 // it does not depend on the grid, the rows per workgroup, the hot set, the host thread count, the
-// backend (host and device give the same bits) or the world size. The flag word is mlr.h's: two
+// backend (host and device give the same bits) or the world size. The flag word is fixedpoint.h's: two
 // 32-bit halves, each written with ordinary stores of the value 1; the low half says that a row's
 // z was not < 2048 (NaN included; such a row's loss counts 2048), the high half names bad input (a
 // label other than 0 / 1, a weight that is negative or not finite, a value that is not finite, a
@@ -42,22 +42,10 @@ FDX_HD bool svc_label_ok(double y) { return y == 0.0 || y == 1.0; }
 
 // ---------------------------------------------------------------- descriptor
 template <class V>
-struct SvcArgs {
-  const int64_t* indptr;     // [rows + 1]
-  const int32_t* idx;
-  const V* val;
+struct SvcArgs : CsrRows<V>, HotSet {   // labels are 0 or 1
   const double* xs;          // [F] scaled coefficients
   double b;                  // intercept
-  const double* labels;      // [rows] 0 or 1
-  const double* weights;     // [rows] or nullptr (1.0)
-  int64_t rows;
-  int32_t F;
   int k, kl;                 // scale exponents of the gradient terms and of the loss
-  // device only: the hot set (no hot set: hot_slots = 0)
-  const uint16_t* slot_of;   // [F] slot of a hot feature, >= hot_slots otherwise
-  const int32_t* hot_feat;   // [hot_slots] feature of a slot
-  int hot_slots;             // hot_slots * 8 <= kNbMaxTableBytes
-  int chunk_rows;            // rows of a workgroup
   // sums, zeroed by the caller
   int64_t* Gq;               // [F]
   int64_t* gbq;              // [1]

@@ -1,14 +1,8 @@
-// Host twin of the linear SVC kernel (contract in svc.h). Every thread owns a range of rows and a
-// private int64 block, and the blocks are merged: the sums are integers, so the thread count does
-// not change a bit. The margin is summed in spmv's order (64 lane-strided partials, halving adds,
-// then + b); the row terms are svc_row_terms, as on the device, so the block equals the device's.
-#include <algorithm>
-#include <atomic>
-#include <stdexcept>
-#include <vector>
-
+// Host twin of the linear SVC kernel (contract in svc.h): its row body on the host pass of
+// fixedpoint.h (private blocks, merged: the thread count does not change a bit). The margin is
+// summed in spmv's order (64 lane-strided partials, halving adds, then + b); the row terms are
+// svc_row_terms, as on the device, so the block equals the device's.
 #include "svc.h"
-#include "parallel_for.h"
 
 namespace fdx {
 
@@ -57,41 +51,14 @@ int64_t svc_rows(const SvcArgs<V>& a, int64_t lo, int64_t hi, uint64_t* G, uint6
 template <class V>
 void svc_eval_cpu(const SvcArgs<V>& a, int threads) {
   if (a.rows <= 0) return;
-  const int64_t width = a.F;
-  int T = threads <= 0 ? HostPool::get().size() : threads;
-  T = (int)std::max<int64_t>(1, std::min<int64_t>(T, a.rows / 256));
-  // thread 0 adds into the outputs themselves
-  std::vector<std::vector<uint64_t>> priv(T > 1 ? T - 1 : 0);
-  std::atomic<int64_t> flags{0};
-  uint64_t sums0[3] = {0, 0, 0};
-  const int64_t per = (a.rows + T - 1) / T;
-  parallel_for(T, T, 1, [&](int64_t lo, int64_t hi) {
-    for (int64_t t = lo; t < hi; ++t) {
-      uint64_t *G, *sums;
-      if (t == 0) {
-        G = reinterpret_cast<uint64_t*>(a.Gq);
-        sums = sums0;
-      } else {
-        priv[t - 1].assign((size_t)width + 3, 0);
-        G = priv[t - 1].data();
-        sums = G + width;
-      }
-      const int64_t f = svc_rows<V>(a, std::min(a.rows, t * per), std::min(a.rows, (t + 1) * per), G, sums);
-      if (f) flags.fetch_or(f, std::memory_order_relaxed);
-    }
-  });
-  uint64_t* out = reinterpret_cast<uint64_t*>(a.Gq);
-  if (T > 1)
-    parallel_for(width, threads, 1 << 14, [&](int64_t lo, int64_t hi) {
-      for (const auto& p : priv)
-        for (int64_t i = lo; i < hi; ++i) out[i] += p[i];
-    });
-  for (const auto& p : priv)
-    for (int i = 0; i < 3; ++i) sums0[i] += p[width + i];
-  *reinterpret_cast<uint64_t*>(a.gbq) += sums0[0];
-  *reinterpret_cast<uint64_t*>(a.lossq) += sums0[1];
-  *reinterpret_cast<uint64_t*>(a.nact) += sums0[2];
-  *a.flag |= flags.load();
+  uint64_t tail[3] = {};                           // gbq, lossq, nact
+  *a.flag |= fx_host_pass(a.rows, threads, reinterpret_cast<uint64_t*>(a.Gq), a.F, tail, 3,
+                          [&](int64_t lo, int64_t hi, uint64_t* G, uint64_t* sums) {
+                            return svc_rows<V>(a, lo, hi, G, sums);
+                          });
+  *reinterpret_cast<uint64_t*>(a.gbq) += tail[0];
+  *reinterpret_cast<uint64_t*>(a.lossq) += tail[1];
+  *reinterpret_cast<uint64_t*>(a.nact) += tail[2];
 }
 template void svc_eval_cpu<float>(const SvcArgs<float>&, int);
 template void svc_eval_cpu<double>(const SvcArgs<double>&, int);

@@ -6,13 +6,9 @@
 // butterfly as spmv does, and every lane then holds the margin and computes the row terms (uniform
 // over the wave). A row inside the margin (residual exactly 0) or with bad input ends there, a
 // wave-uniform branch: near the optimum most rows do. Only an active row walks its entries again
-// (they are in L1 / L2) and adds rint(x r 2^k) per entry: a feature of the hot set
-// (slot_of[f] < hot_slots) adds into the workgroup's int64 LDS table [H] with a 64-bit LDS atomic,
-// every other entry goes straight to a global integer atomic; zero terms are skipped. The table's
-// non-zero slots are flushed with 64-bit integer global atomics when the chunk is done. The
-// intercept sum, the loss and the active-row count are summed per wave in registers, then in LDS,
-// and leave the workgroup as at most three global atomics. Integer adds commute, so the hot set,
-// the chunk size and the grid change the speed only.
+// (they are in L1 / L2) and adds rint(x r 2^k) per entry into the table [H] or Gq (the fixed-point
+// row pass of fixedpoint.h with C = 1); zero terms are skipped. The intercept sum, the loss and the
+// active-row count are the scalar sums: at most three global atomics.
 #include <stdexcept>
 
 #include "svc.h"
@@ -23,26 +19,19 @@ namespace fdx {
 
 namespace {
 
-using u64 = unsigned long long;
-
-__device__ __forceinline__ double svc_wave_sum(double v) {
-#pragma unroll
-  for (int o = kNbWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kNbWave);
-  return v;
-}
+using u64 = fx_u64;
 
 template <class V>
 __global__ __launch_bounds__(kNbBlock) void svc_eval_kernel(SvcArgs<V> a) {
   extern __shared__ u64 table[];                 // [hot_slots]
   __shared__ u64 sums_s[3];                      // gbq, lossq, nact
   const int tid = threadIdx.x, lane = tid & (kNbWave - 1), wave = tid / kNbWave;
-  const int H = a.hot_slots;
-  for (int i = tid; i < H; i += kNbBlock) table[i] = 0;
+  fx_table_zero(table, a.hot_slots);
   if (tid < 3) sums_s[tid] = 0;
   __syncthreads();
 
-  const int64_t r0 = (int64_t)blockIdx.x * a.chunk_rows;
-  const int64_t r1 = r0 + a.chunk_rows < a.rows ? r0 + a.chunk_rows : a.rows;
+  int64_t r0, r1;
+  fx_chunk(a, a.rows, r0, r1);
   const double bias = a.b;
   u64 gb = 0, lossq = 0, nact = 0;               // uniform over the wave
   bool bad = false, clamped_any = false;
@@ -60,7 +49,7 @@ __global__ __launch_bounds__(kNbBlock) void svc_eval_kernel(SvcArgs<V> a) {
       bad_row |= !mlr_value_ok(x);
       m += x * a.xs[f];
     }
-    m = svc_wave_sum(m) + bias;
+    m = fx_wave_sum(m) + bias;
     bad_row = __any(bad_row);
     double res = 0.0, loss = 0.0;
     if (bad_row) {
@@ -83,30 +72,19 @@ __global__ __launch_bounds__(kNbBlock) void svc_eval_kernel(SvcArgs<V> a) {
       const int32_t f = a.idx[j];                // in range: the row is not bad
       const u64 q = (u64)nb_quant((double)a.val[j] * res, a.k);
       if (q == 0) continue;
-      const int slot = H ? (int)a.slot_of[f] : (int)kNbCold;
-      atomicAdd(slot < H ? table + slot : G + f, q);
+      atomicAdd(fx_dst<1>(a, table, G, f), q);
     }
   }
   if (lane == 0) {
-    if (gb) atomicAdd(&sums_s[0], gb);
-    if (lossq) atomicAdd(&sums_s[1], lossq);
-    if (nact) atomicAdd(&sums_s[2], nact);
+    fx_sum_to_lds(&sums_s[0], gb);
+    fx_sum_to_lds(&sums_s[1], lossq);
+    fx_sum_to_lds(&sums_s[2], nact);
   }
-  // every writer stores the same value into its half of the flag word
-  if (clamped_any) reinterpret_cast<int32_t*>(a.flag)[0] = 1;
-  if (bad) reinterpret_cast<int32_t*>(a.flag)[1] = 1;
+  fx_flag(a.flag, clamped_any, bad);
   __syncthreads();
-  for (int i = tid; i < H; i += kNbBlock) {
-    const u64 v = table[i];
-    if (v == 0) continue;
-    const int32_t f = a.hot_feat[i];
-    if ((uint32_t)f < (uint32_t)a.F) atomicAdd(G + f, v);
-  }
-  if (tid < 3 && sums_s[tid]) {
-    // the three sums are adjacent in the block only by the caller's choice: address each
-    int64_t* const dst = tid == 0 ? a.gbq : tid == 1 ? a.lossq : a.nact;
-    atomicAdd(reinterpret_cast<u64*>(dst), sums_s[tid]);
-  }
+  fx_flush<1>(a, table, G, a.F);
+  // the three sums are adjacent in the block only by the caller's choice: address each
+  if (tid < 3) fx_sum_to_global(tid == 0 ? a.gbq : tid == 1 ? a.lossq : a.nact, sums_s[tid]);
 }
 
 }  // namespace
@@ -114,11 +92,8 @@ __global__ __launch_bounds__(kNbBlock) void svc_eval_kernel(SvcArgs<V> a) {
 template <class V>
 void launch_svc_eval(const SvcArgs<V>& a, hipStream_t stream) {
   if (a.rows <= 0) return;
-  if (a.chunk_rows < 1 || a.hot_slots < 0 || (int64_t)a.hot_slots * 8 > kNbMaxTableBytes)
-    throw std::runtime_error("fdx svc_eval: chunk or hot set out of range");
-  const size_t lds = (size_t)a.hot_slots * sizeof(u64);
-  const unsigned grid = (unsigned)nb_chunks(a.rows, a.chunk_rows);
-  hipLaunchKernelGGL(svc_eval_kernel<V>, dim3(grid), dim3(kNbBlock), lds, stream, a);
+  const FxLaunch l = fx_launch("svc_eval", 1, 1, a, a.rows);
+  hipLaunchKernelGGL(svc_eval_kernel<V>, dim3(l.grid), dim3(kNbBlock), l.lds, stream, a);
 }
 template void launch_svc_eval<float>(const SvcArgs<float>&, hipStream_t);
 template void launch_svc_eval<double>(const SvcArgs<double>&, hipStream_t);

@@ -5,7 +5,7 @@
 // contract names, so a read or write past them is an AddressSanitizer report. The scores are
 // compared bit for bit with the lane-order sum taken here over the CSR the same call wrote. Built
 // with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_cls_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("cls"); exits non-zero on failure.
 #include <cstdio>
 #include <cstring>
 #include <string>

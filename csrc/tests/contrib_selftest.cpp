@@ -1,7 +1,7 @@
 // Stand-alone self-test of the TreeSHAP host twin (contrib_cpu.cpp) for sanitizer builds: a small
 // hand-made ensemble against hand-computed values, including the empty row, a path without
 // elements (d = 0) and a path at the depth limit (d = 32). Built with -fsanitize=address,undefined
-// by fraud_detection_spark_kafka_llm_amd/_build.py:build_contrib_selftest(); exits non-zero on failure.
+// by fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("contrib"); exits non-zero on failure.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

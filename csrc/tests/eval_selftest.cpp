@@ -2,7 +2,7 @@
 // builds: a hand-made node table over rows with absent features, an empty row, a value exactly on
 // a threshold and a malformed table; the fixed-point sums and the AUC integers against values
 // computed by hand, including ties, signed zeros, a one-class set and the empty set. Built with
-// -fsanitize=address,undefined by fraud_detection_spark_kafka_llm_amd/_build.py:build_eval_selftest();
+// -fsanitize=address,undefined by fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("eval");
 // exits non-zero on failure.
 #include <cmath>
 #include <cstdio>

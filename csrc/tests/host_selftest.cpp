@@ -1,7 +1,7 @@
 // Host-path self-test for sanitizer builds: exercises the multi-threaded CPU
 // implementations (featurizer incl. token keys, JSON extraction, tree engine) on edge cases and
 // checks them against simple scalar references. Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_host_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("host"); exits non-zero on failure.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

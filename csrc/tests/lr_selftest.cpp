@@ -4,7 +4,7 @@
 // 65537 slots (buffers sized exactly, so a read or write past the intercept slot is caught), the
 // projection to exact zeros, and the sums against the same tree fed with the per-element outputs.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_lr_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("lr"); exits non-zero on failure.
 #include <cmath>
 #include <cstdio>
 #include <cstring>

@@ -7,7 +7,7 @@
 // labels, weights, values and feature ids must set the high half of the flag word and add nothing,
 // and no value that is not finite may reach a conversion to an integer.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_mlr_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("mlr"); exits non-zero on failure.
 #include <cmath>
 #include <cstdio>
 #include <cstring>

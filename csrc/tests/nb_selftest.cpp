@@ -5,7 +5,7 @@
 // evaluation of the contract and across the thread counts, scores bit for bit with the lane-order
 // sum; bad labels, weights, values and feature ids must set the flag word and add nothing.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_nb_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("nb"); exits non-zero on failure.
 #include <cmath>
 #include <cstdio>
 #include <cstring>

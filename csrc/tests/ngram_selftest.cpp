@@ -3,7 +3,7 @@
 // separated by removed stop words, runs of double spaces, a tab/newline document without cleaning
 // and all pairs of 1..5-letter tokens, in hashing, vocabulary and keys mode on several threads,
 // against n-grams formed as plain strings. Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_ngram_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("ngram"); exits non-zero on failure.
 #include <cstdio>
 #include <map>
 #include <string>

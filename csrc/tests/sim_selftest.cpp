@@ -5,7 +5,7 @@
 // exactly, so a read or write past a row, a query or a candidate list is caught. Results are
 // compared bit for bit with a direct evaluation of the contract and across the work splits.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_sim_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("sim"); exits non-zero on failure.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -8,7 +8,7 @@
 // against a direct lane-order evaluation. Every buffer is sized exactly, so a read or write past a
 // row, a plane or the tree list is caught.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_softprob_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("softprob"); exits non-zero on failure.
 #include <cmath>
 #include <cstdio>
 #include <cstring>

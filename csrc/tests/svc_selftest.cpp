@@ -7,7 +7,7 @@
 // feature ids must set the high half of the flag word and add nothing, and no value that is not
 // finite may reach a conversion to an integer.
 // Built with -fsanitize=address,undefined by
-// fraud_detection_spark_kafka_llm_amd/_build.py:build_svc_selftest(); exits non-zero on failure.
+// fraud_detection_spark_kafka_llm_amd/_build.py:build_selftest("svc"); exits non-zero on failure.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -225,6 +225,19 @@ static void test_flags() {
   EXPECT(svc_label_ok(0.0) && svc_label_ok(1.0) && !svc_label_ok(0.5) && !svc_label_ok(nan));
 }
 
+// the shared host pass (fixedpoint.h) at 2 * 256 + 1 rows: whatever the thread count asked for, the
+// private blocks merge to the single-thread block
+static void test_host_merge() {
+  const Data<double> d = make<double>(2 * 256 + 1 - kHead - 6, false, 0.25);
+  EXPECT(d.rows() == 2 * 256 + 1);
+  const Out ref = run(d, true, 38, 36, 1, true);
+  EXPECT(ref.block.back() == 0 && ref.block == direct(d, true, 38, 36));
+  for (int threads : {1, 2, 7}) {
+    const Out o = run(d, true, 38, 36, threads, true);
+    EXPECT(o.block == ref.block && o.r == ref.r && o.loss == ref.loss && o.margin == ref.margin);
+  }
+}
+
 static void test_empty() {
   Data<double> d;
   d.xs.assign((size_t)d.F, 0.0);
@@ -241,6 +254,7 @@ int main() {
   test_eval<float>();
   test_clamp();
   test_flags();
+  test_host_merge();
   test_empty();
   if (g_fail) {
     std::fprintf(stderr, "svc selftest: %d failure(s)\n", g_fail);

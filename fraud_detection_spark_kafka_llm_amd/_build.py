@@ -142,207 +142,39 @@ SELFTEST_ENV = {"ASAN_OPTIONS": "detect_odr_violation=0:abort_on_error=1:detect_
 HOST_SOURCES = ("text_cpu.cpp", "sparse_cpu.cpp", "tree_cpu.cpp", "json_text.cpp", "json_encode.cpp")
 
 
-def build_host_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """Debug target of SURVEY §5.2: the host (CPU) implementations + ``csrc/tests/host_selftest.cpp``
-    as a standalone executable, built with AddressSanitizer + UndefinedBehaviorSanitizer (host
-    code only: no device code is compiled into it)."""
+# name -> (host sources linked in, what the self-test covers); the test file is csrc/tests/<name>_selftest.cpp
+SELFTESTS = {
+    "host": (HOST_SOURCES, "host (CPU) implementations (SURVEY §5.2)"),
+    "contrib": (("contrib_cpu.cpp",), "TreeSHAP host twin"),
+    "eval": (("eval_cpu.cpp",), "validation-monitoring host twins"),
+    "ngram": (("text_cpu.cpp",), "n-gram mode of the featurizer's host twin"),
+    "cls": (("text_cpu.cpp",), "class-score tail of the featurizer's host twin"),
+    "lr": (("sparse_cpu.cpp", "lr_cpu.cpp"), "elastic-net logistic-regression host twins"),
+    "sim": (("sim_cpu.cpp",), "top-k cosine retrieval host twins"),
+    "nb": (("nb_cpu.cpp",), "Naive Bayes host twins"),
+    "mlr": (("nb_cpu.cpp", "mlr_cpu.cpp"), "multinomial logistic-regression host twin"),
+    "softprob": (("softprob_cpu.cpp",), "multi-class boosting host twins"),
+    "svc": (("svc_cpu.cpp",), "linear SVC host twin"),
+}
+
+
+def build_selftest(name: str, sanitize: bool = True, out: Path | None = None) -> Path:
+    """The host sources of ``SELFTESTS[name]`` + ``csrc/tests/<name>_selftest.cpp`` as a standalone
+    executable, built with AddressSanitizer + UndefinedBehaviorSanitizer (host code only: no device
+    code is compiled into it)."""
+    sources, _ = SELFTESTS[name]
     hipcc = _hipcc()
-    out = out or (BUILD / ("host_selftest_asan" if sanitize else "host_selftest"))
+    out = out or (BUILD / (f"{name}_selftest_asan" if sanitize else f"{name}_selftest"))
     out.parent.mkdir(parents=True, exist_ok=True)
     flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
              "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
     if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize",
-                  ]
+        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
     # one translation unit (unity build): inline functions of libstdc++ then exist once, so ASan
     # does not see the same COMDAT string literal registered by several objects (false ODR report)
-    unity = out.parent / "host_selftest_unity.cpp"
-    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in HOST_SOURCES)
-                     + f'#include "{CSRC / "tests" / "host_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_contrib_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/contrib_selftest.cpp`` + the TreeSHAP host twin (``contrib_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_host_selftest`` (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("contrib_selftest_asan" if sanitize else "contrib_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "contrib_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "contrib_cpu.cpp"}"\n#include "{CSRC / "tests" / "contrib_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_eval_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/eval_selftest.cpp`` + the validation-monitoring host twins (``eval_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_contrib_selftest`` (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("eval_selftest_asan" if sanitize else "eval_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "eval_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "eval_cpu.cpp"}"\n#include "{CSRC / "tests" / "eval_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_ngram_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/ngram_selftest.cpp`` + the fused featurizer's host twin (``text_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_eval_selftest`` (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("ngram_selftest_asan" if sanitize else "ngram_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "ngram_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "text_cpu.cpp"}"\n#include "{CSRC / "tests" / "ngram_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_cls_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/cls_selftest.cpp`` + the fused featurizer's host twin (``text_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_ngram_selftest`` (host code only, one translation unit): the class-score tail."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("cls_selftest_asan" if sanitize else "cls_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "cls_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "text_cpu.cpp"}"\n#include "{CSRC / "tests" / "cls_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_lr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/lr_selftest.cpp`` + the elastic-net logistic-regression host twins (``lr_cpu.cpp``, and
-    ``sparse_cpu.cpp`` for the SpMV the margins must equal) as a standalone executable under
-    AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_eval_selftest`` (host code only,
-    one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("lr_selftest_asan" if sanitize else "lr_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "lr_selftest_unity.cpp"
-    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in ("sparse_cpu.cpp", "lr_cpu.cpp"))
-                     + f'#include "{CSRC / "tests" / "lr_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_sim_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/sim_selftest.cpp`` + the top-k cosine retrieval host twins (``sim_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_lr_selftest`` (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("sim_selftest_asan" if sanitize else "sim_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "sim_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "sim_cpu.cpp"}"\n#include "{CSRC / "tests" / "sim_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_nb_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/nb_selftest.cpp`` + the Naive Bayes host twins (``nb_cpu.cpp``) as a standalone
-    executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_sim_selftest``
-    (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("nb_selftest_asan" if sanitize else "nb_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "nb_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "nb_cpu.cpp"}"\n#include "{CSRC / "tests" / "nb_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_mlr_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/mlr_selftest.cpp`` + the multinomial logistic-regression host twin (``mlr_cpu.cpp``, and
-    ``nb_cpu.cpp`` for the class scores the margins must equal) as a standalone executable under
-    AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_nb_selftest`` (host code only,
-    one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("mlr_selftest_asan" if sanitize else "mlr_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "mlr_selftest_unity.cpp"
-    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in ("nb_cpu.cpp", "mlr_cpu.cpp"))
-                     + f'#include "{CSRC / "tests" / "mlr_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_softprob_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/softprob_selftest.cpp`` + the multi-class boosting host twins (``softprob_cpu.cpp``) as a
-    standalone executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like
-    ``build_mlr_selftest`` (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("softprob_selftest_asan" if sanitize else "softprob_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "softprob_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "softprob_cpu.cpp"}"\n#include "{CSRC / "tests" / "softprob_selftest.cpp"}"\n')
-    link = ["-fsanitize=address,undefined"] if sanitize else []
-    _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
-    return out
-
-
-def build_svc_selftest(sanitize: bool = True, out: Path | None = None) -> Path:
-    """``csrc/tests/svc_selftest.cpp`` + the linear SVC host twin (``svc_cpu.cpp``) as a standalone
-    executable under AddressSanitizer + UndefinedBehaviorSanitizer, built like ``build_mlr_selftest``
-    (host code only, one translation unit)."""
-    hipcc = _hipcc()
-    out = out or (BUILD / ("svc_selftest_asan" if sanitize else "svc_selftest"))
-    out.parent.mkdir(parents=True, exist_ok=True)
-    flags = ["-O1", "-g", "-std=c++17", f"-I{CSRC}", "-I/opt/rocm/include", "-x", "c++", "-D__HIP_PLATFORM_AMD__=1",
-             "-pthread", "-ffp-contract=off", "-fno-omit-frame-pointer"]
-    if sanitize:
-        flags += ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-gpu-sanitize"]
-    unity = out.parent / "svc_selftest_unity.cpp"
-    unity.write_text(f'#include "{CSRC / "svc_cpu.cpp"}"\n#include "{CSRC / "tests" / "svc_selftest.cpp"}"\n')
+    unity = out.parent / f"{name}_selftest_unity.cpp"
+    unity.write_text("".join(f'#include "{CSRC / s}"\n' for s in sources)
+                     + f'#include "{CSRC / "tests" / f"{name}_selftest.cpp"}"\n')
     link = ["-fsanitize=address,undefined"] if sanitize else []
     _run([hipcc, *flags, str(unity), "-o", str(out), "-pthread", *link])
     return out
@@ -353,48 +185,13 @@ def main(argv=None) -> int:
     ap.add_argument("--force", action="store_true")
     ap.add_argument("-j", "--jobs", type=int, default=None)
     ap.add_argument("-v", "--verbose", action="store_true")
-    ap.add_argument("--host-selftest", action="store_true", help="build + run the ASan/UBSan host self-test")
-    ap.add_argument("--contrib-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the TreeSHAP host twin")
-    ap.add_argument("--eval-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the validation-monitoring host twins")
-    ap.add_argument("--ngram-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the n-gram mode of the featurizer's host twin")
-    ap.add_argument("--lr-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the elastic-net logistic-regression host twins")
-    ap.add_argument("--sim-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the top-k cosine retrieval host twins")
-    ap.add_argument("--nb-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the Naive Bayes host twins")
-    ap.add_argument("--mlr-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the multinomial logistic-regression host twin")
-    ap.add_argument("--cls-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the class-score tail of the featurizer's host twin")
-    ap.add_argument("--softprob-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the multi-class boosting host twins")
-    ap.add_argument("--svc-selftest", action="store_true",
-                    help="build + run the ASan/UBSan self-test of the linear SVC host twin")
+    for name, (_, what) in SELFTESTS.items():
+        ap.add_argument(f"--{name}-selftest", action="store_true",
+                        help=f"build + run the ASan/UBSan self-test of the {what}")
     args = ap.parse_args(argv)
-    if args.svc_selftest:
-        return subprocess.run([str(build_svc_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.softprob_selftest:
-        return subprocess.run([str(build_softprob_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.cls_selftest:
-        return subprocess.run([str(build_cls_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.mlr_selftest:
-        return subprocess.run([str(build_mlr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.nb_selftest:
-        return subprocess.run([str(build_nb_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.sim_selftest:
-        return subprocess.run([str(build_sim_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.lr_selftest:
-        return subprocess.run([str(build_lr_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.ngram_selftest:
-        return subprocess.run([str(build_ngram_selftest())], env={**os.environ, **SELFTEST_ENV}).returncode
-    if args.host_selftest or args.contrib_selftest or args.eval_selftest:
-        exe = build_host_selftest() if args.host_selftest else \
-            (build_contrib_selftest() if args.contrib_selftest else build_eval_selftest())
-        return subprocess.run([str(exe)], env={**os.environ, **SELFTEST_ENV}).returncode
+    for name in SELFTESTS:
+        if getattr(args, f"{name}_selftest"):
+            return subprocess.run([str(build_selftest(name))], env={**os.environ, **SELFTEST_ENV}).returncode
     path = build(force=args.force, jobs=args.jobs, verbose=args.verbose)
     print(f"built {path}")
     return 0

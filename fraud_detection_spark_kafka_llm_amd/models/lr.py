@@ -34,38 +34,12 @@ import torch
 from ..ml.linalg import VectorColumn
 from ..ops import native
 from ..ops.sparse import _csr as sparse_csr
-from ..ops.sparse import (lr_forward, lr_owlqn_step, lr_pseudo_grad, mlr_eval, mlr_limits, mlr_scale_exponents,
-                          nb_hot_set, nb_hot_tables, spmv)
+from ..ops.sparse import lr_forward, lr_owlqn_step, lr_pseudo_grad, mlr_eval, mlr_limits, mlr_scale_exponents, spmv
 from ..parallel import dist as D
 from ..parallel.dist import Collectives
 from ..utils.config import default_device
-
-
-def transpose_csr(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, num_cols: int) -> tuple:
-    """CSR of X^T: entries stably sorted by column, so each column keeps its rows ascending."""
-    n = indptr.numel() - 1
-    counts = indptr[1:] - indptr[:-1]
-    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=idx.device), counts,
-                                   output_size=int(idx.numel()))
-    order = torch.sort(idx.to(torch.int64), stable=True).indices
-    t_indptr = torch.zeros(num_cols + 1, dtype=torch.int64, device=idx.device)
-    torch.cumsum(torch.bincount(idx.to(torch.int64), minlength=num_cols), 0, out=t_indptr[1:])
-    return t_indptr, rows[order].contiguous(), val[order].contiguous()
-
-
-def _feature_scale(xt, t_val, w, wsum, coll, F: int, standardization: bool) -> torch.Tensor:
-    """``1 / std`` of every feature (sample std over all ranks, constant features 0) with
-    ``standardization``, ones without; ``xt(v, vals)`` is the fixed-order ``X^T v``."""
-    if standardization:
-        s1 = coll.sum(xt(w))
-        s2 = coll.sum(xt(w, t_val * t_val))
-        mean = s1 / wsum
-        var = (s2 - wsum * mean * mean) / max(wsum - 1.0, 1.0)
-        std = torch.sqrt(torch.clamp(var, min=0.0))
-        scale = torch.where(std > 0, 1.0 / torch.where(std > 0, std, torch.ones_like(std)), torch.zeros_like(std))
-    else:
-        scale = torch.ones(F, dtype=torch.float64, device=w.device)
-    return scale
+from ._linear_common import (_feature_scale, _raise_bad_input, coerce_rows, hot_tables, reduce_statistics,
+                             signed_extremes, transpose_csr, weight_sum_and_scale)
 
 
 def _lbfgs(fg, theta: torch.Tensor, max_iter: int, tol: float, history_size: int):
@@ -316,17 +290,6 @@ def label_maximum(labels, device=None) -> float:
     return float(m[0])
 
 
-def _mlr_raise(idx, val, y, w, C: int, F: int) -> None:
-    """Name the bad input behind the pass's flag word (the slow path: only taken on an error)."""
-    if not bool(torch.all((y >= 0) & (y < C) & (y == torch.floor(y)))):
-        raise ValueError(f"multinomial logistic regression labels must be integers in 0 .. {C - 1}")
-    if w is not None and not bool(torch.all(torch.isfinite(w) & (w >= 0))):
-        raise ValueError("multinomial logistic regression weights must be finite and >= 0")
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
-        raise ValueError("feature index outside the feature space")
-    raise ValueError("multinomial logistic regression requires finite feature values")
-
-
 # counters of the last multinomial fit: read by the profile note and the micro-benchmark only
 MLR_STATS = {"evaluations": 0, "iterations": 0, "k": 0, "kl": 0}
 
@@ -352,30 +315,10 @@ def train_multinomial_logistic_regression(features, labels, weights=None, max_it
     if reg_param > 0 and elastic_net > 0:
         raise NotImplementedError("multinomial logistic regression supports elasticNetParam = 0 only "
                                   "(no L1 part)")
-    dev = torch.device(device) if device is not None else default_device()
-    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
-    vc = vc.to(dev)
+    dev, vc, y, w, n = coerce_rows(features, labels, weights, device)
     indptr, idx, val = sparse_csr(vc)
-    F, n = int(vc.size), len(vc)
-    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
-                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64).contiguous()
-    w = None if weights is None else torch.as_tensor(
-        weights if isinstance(weights, (torch.Tensor, np.ndarray)) else np.asarray(weights, dtype=np.float64)
-    ).to(device=dev, dtype=torch.float64).contiguous()
-    if y.numel() != n or (w is not None and w.numel() != n):
-        raise ValueError("labels and weights need one entry per row")
-    # (largest label, - smallest label, largest weight, - smallest weight, largest |value|): one small
-    # copy, MAX over the ranks (a NaN survives every maximum)
-    zero, one = y.new_zeros(()), y.new_ones(())
-    stats = torch.stack([y.max() if n else zero, -y.min() if n else zero,
-                         w.max() if w is not None and n else one, -w.min() if w is not None and n else -one,
-                         val.abs().max().to(torch.float64) if val.numel() else zero])
-    rows = torch.tensor([n], dtype=torch.int64, device=dev)
-    if D.is_dist():
-        stats = D.all_reduce_max(stats)
-        rows = D.all_reduce_sum(rows)
-    ymax, ymin_neg, wmax, wmin_neg, vmax = (float(v) for v in stats.cpu())
-    n_global = int(rows[0])
+    F = int(vc.size)
+    (ymax, ymin_neg, wmax, wmin_neg, vmax), n_global = reduce_statistics(signed_extremes(y, w, val, n), n, dev)
     lim = mlr_limits()
     if not (math.isfinite(ymax) and math.isfinite(ymin_neg)) or ymin_neg > 0 or ymax != math.floor(ymax):
         raise ValueError("multinomial logistic regression labels must be integers in 0 .. C - 1")
@@ -388,28 +331,10 @@ def train_multinomial_logistic_regression(features, labels, weights=None, max_it
     if not math.isfinite(vmax):
         raise ValueError("multinomial logistic regression requires finite feature values")
     k, kl = mlr_scale_exponents(wmax, vmax, n_global)
-    coll = Collectives()
-    w_rows = torch.ones(n, dtype=torch.float64, device=dev) if w is None else w
+    coll, w_rows, wsum, scale = weight_sum_and_scale(indptr, idx, val, F, w, n, standardization,
+                                                     "multinomial logistic regression")
     class_w = coll.sum(torch.stack([(w_rows * (y == c)).sum() for c in range(C)]))
-    wsum = float(coll.sum(w_rows.sum().reshape(1))[0])
-    if not wsum > 0:
-        raise ValueError("multinomial logistic regression needs a positive weight sum")
-    if standardization:
-        val64 = val.to(torch.float64)
-        t_indptr, t_idx, t_val = transpose_csr(indptr, idx, val64, F)
-
-        def xt(v: torch.Tensor, vals: Optional[torch.Tensor] = None) -> torch.Tensor:
-            return spmv(t_indptr, t_idx, t_val if vals is None else vals, v)
-
-        scale = _feature_scale(xt, t_val, w_rows, wsum, coll, F, True)
-        del t_indptr, t_idx, t_val, val64
-    else:
-        scale = _feature_scale(None, None, w_rows, wsum, coll, F, False)
-    hot_tables = (None, None)
-    if dev.type == "cuda":
-        hot_feat = nb_hot_set(indptr, idx, val, F, C) if hot is None else \
-            torch.as_tensor(hot, dtype=torch.int32, device=dev).reshape(-1)
-        hot_tables = nb_hot_tables(hot_feat, F, C)
+    tables = hot_tables(indptr, idx, val, F, C, hot)
     inv_k = math.ldexp(1.0, -k)
     stats_ = MLR_STATS
     stats_.update(evaluations=0, iterations=0, k=k, kl=kl)
@@ -417,13 +342,13 @@ def train_multinomial_logistic_regression(features, labels, weights=None, max_it
     def fg(theta: torch.Tensor):
         B, b = theta[:C * F].view(C, F), theta[C * F:]
         XS = (scale.unsqueeze(1) * B.t()).contiguous()
-        res = mlr_eval(indptr, idx, val, XS, b.contiguous(), y, w, k, kl, hot_tables, chunk_rows=chunk_rows,
+        res = mlr_eval(indptr, idx, val, XS, b.contiguous(), y, w, k, kl, tables, chunk_rows=chunk_rows,
                        check_extents=stats_["evaluations"] == 0, threads=threads)
         block = coll.sum(res.block)
         tail = block[-2:].cpu()
         lossq, flag = int(tail[0]), int(tail[1])
         if flag >> 32:
-            _mlr_raise(idx, val, y, w, C, F)
+            _raise_bad_input("mlr", idx, val, y, w, F, C)
         first = stats_["evaluations"] == 0
         stats_["evaluations"] += 1
         g = torch.empty_like(theta)

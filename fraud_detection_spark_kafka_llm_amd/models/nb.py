@@ -15,10 +15,9 @@ import math
 import numpy as np
 import torch
 
-from ..ml.linalg import VectorColumn
 from ..ops.sparse import nb_limits, nb_scale_exponent, nb_sums
 from ..parallel import dist as D
-from ..utils.config import default_device
+from ._linear_common import coerce_rows, reduce_statistics
 
 MODEL_TYPES = ("multinomial", "bernoulli")
 
@@ -83,28 +82,12 @@ def fit_naive_bayes(features, labels, weights=None, smoothing: float = 1.0, mode
     if not float(smoothing) >= 0.0:
         raise ValueError(f"smoothing must be >= 0, got {smoothing}")
     bernoulli = model_type == "bernoulli"
-    dev = torch.device(device) if device is not None else default_device()
-    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
-    vc = vc.to(dev)
+    dev, vc, y, w, n = coerce_rows(features, labels, weights, device)
     val = vc.csr()[2]
-    n = len(vc)
-    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
-                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64)
-    w = None if weights is None else torch.as_tensor(
-        weights if isinstance(weights, (torch.Tensor, np.ndarray)) else np.asarray(weights, dtype=np.float64)
-    ).to(device=dev, dtype=torch.float64)
-    if y.numel() != n or (w is not None and w.numel() != n):
-        raise ValueError("labels and weights need one entry per row")
-    # (largest label, largest weight, largest value, rows): one small copy, MAX / SUM over the ranks
-    stats = torch.stack([y.max() if n else y.new_zeros(()),
-                         w.max() if w is not None and n else y.new_ones(()),
-                         val.max().to(torch.float64) if val.numel() else y.new_zeros(())])
-    rows = torch.tensor([n], dtype=torch.int64, device=dev)
-    if D.is_dist():
-        stats = D.all_reduce_max(stats)
-        rows = D.all_reduce_sum(rows)
-    ymax, wmax, vmax = (float(v) for v in stats.cpu())
-    n_global = int(rows[0])
+    # (largest label, largest weight, largest value)
+    (ymax, wmax, vmax), n_global = reduce_statistics(
+        [y.max() if n else y.new_zeros(()), w.max() if w is not None and n else y.new_ones(()),
+         val.max().to(torch.float64) if val.numel() else y.new_zeros(())], n, dev)
     lim = nb_limits()
     if not math.isfinite(ymax) or ymax < 0 or ymax != math.floor(ymax):
         raise ValueError("Naive Bayes labels must be integers in 0 .. C - 1")

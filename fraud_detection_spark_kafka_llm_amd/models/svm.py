@@ -6,33 +6,18 @@ of a parameter vector are the same bits on the host, on the device and for every
 from __future__ import annotations
 
 import math
-from typing import Optional
 
-import numpy as np
 import torch
 
-from ..ml.linalg import VectorColumn
 from ..ops.sparse import _csr as sparse_csr
-from ..ops.sparse import mlr_scale_exponents, nb_hot_set, nb_hot_tables, spmv, svc_eval, svc_limits
-from ..parallel import dist as D
-from ..parallel.dist import Collectives
-from ..utils.config import default_device
-from .lr import _feature_scale, _lbfgs, transpose_csr
+from ..ops.sparse import mlr_scale_exponents, svc_eval, svc_limits
+from ._linear_common import (_raise_bad_input, coerce_rows, hot_tables, reduce_statistics, signed_extremes,
+                             weight_sum_and_scale)
+from .lr import _lbfgs
 
 # counters of the last fit (evaluations, iterations, the scale exponents and the share of rows with a
 # non-zero residual in the last evaluation): read by the profile note and the micro-benchmark only
 SVC_STATS = {"evaluations": 0, "iterations": 0, "k": 0, "kl": 0, "active_share": 0.0}
-
-
-def _svc_raise(idx, val, y, w, F: int) -> None:
-    """Name the bad input behind the pass's flag word (the slow path: only taken on an error)."""
-    if not bool(torch.all((y == 0) | (y == 1))):
-        raise ValueError("LinearSVC labels must be 0 or 1")
-    if w is not None and not bool(torch.all(torch.isfinite(w) & (w >= 0))):
-        raise ValueError("LinearSVC weights must be finite and >= 0")
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
-        raise ValueError("feature index outside the feature space")
-    raise ValueError("LinearSVC requires finite feature values")
 
 
 def train_linear_svc(features, labels, weights=None, max_iter: int = 100, tol: float = 1e-6,
@@ -47,31 +32,13 @@ def train_linear_svc(features, labels, weights=None, max_iter: int = 100, tol: f
     ``nb_hot_set``), ``chunk_rows`` and ``threads`` change the speed only."""
     if reg_param < 0:
         raise ValueError(f"reg_param must be >= 0, got {reg_param}")
-    dev = torch.device(device) if device is not None else default_device()
-    vc = features if isinstance(features, VectorColumn) else VectorColumn.from_rows(list(features))
-    vc = vc.to(dev)
+    dev, vc, y, w, n = coerce_rows(features, labels, weights, device)
     indptr, idx, val = sparse_csr(vc)
-    F, n = int(vc.size), len(vc)
-    y = torch.as_tensor(labels if isinstance(labels, (torch.Tensor, np.ndarray)) else
-                        np.asarray([float(v) for v in labels])).to(device=dev, dtype=torch.float64).contiguous()
-    w = None if weights is None else torch.as_tensor(
-        weights if isinstance(weights, (torch.Tensor, np.ndarray)) else np.asarray(weights, dtype=np.float64)
-    ).to(device=dev, dtype=torch.float64).contiguous()
-    if y.numel() != n or (w is not None and w.numel() != n):
-        raise ValueError("labels and weights need one entry per row")
-    # (largest label, - smallest label, largest weight, - smallest weight, largest |value|, rows whose
-    # label is neither 0 nor 1): one small copy, MAX over the ranks (a NaN survives every maximum)
-    zero, one = y.new_zeros(()), y.new_ones(())
-    stats = torch.stack([y.max() if n else zero, -y.min() if n else zero,
-                         w.max() if w is not None and n else one, -w.min() if w is not None and n else -one,
-                         val.abs().max().to(torch.float64) if val.numel() else zero,
-                         ((y != 0) & (y != 1)).sum().to(torch.float64)])
-    rows = torch.tensor([n], dtype=torch.int64, device=dev)
-    if D.is_dist():
-        stats = D.all_reduce_max(stats)
-        rows = D.all_reduce_sum(rows)
-    ymax, ymin_neg, wmax, wmin_neg, vmax, odd = (float(v) for v in stats.cpu())
-    n_global = int(rows[0])
+    F = int(vc.size)
+    # the sixth statistic: rows whose label is neither 0 nor 1
+    odd_rows = ((y != 0) & (y != 1)).sum().to(torch.float64)
+    (ymax, ymin_neg, wmax, wmin_neg, vmax, odd), n_global = reduce_statistics(
+        signed_extremes(y, w, val, n) + [odd_rows], n, dev)
     if not (math.isfinite(ymax) and math.isfinite(ymin_neg)) or odd != 0:
         raise ValueError("LinearSVC labels must be 0 or 1")
     if not (math.isfinite(wmax) and math.isfinite(wmin_neg)) or wmin_neg > 0:
@@ -79,27 +46,8 @@ def train_linear_svc(features, labels, weights=None, max_iter: int = 100, tol: f
     if not math.isfinite(vmax):
         raise ValueError("LinearSVC requires finite feature values")
     k, kl = mlr_scale_exponents(wmax, vmax, n_global)
-    coll = Collectives()
-    w_rows = torch.ones(n, dtype=torch.float64, device=dev) if w is None else w
-    wsum = float(coll.sum(w_rows.sum().reshape(1))[0])
-    if not wsum > 0:
-        raise ValueError("LinearSVC needs a positive weight sum")
-    if standardization:
-        val64 = val.to(torch.float64)
-        t_indptr, t_idx, t_val = transpose_csr(indptr, idx, val64, F)
-
-        def xt(v: torch.Tensor, vals: Optional[torch.Tensor] = None) -> torch.Tensor:
-            return spmv(t_indptr, t_idx, t_val if vals is None else vals, v)
-
-        scale = _feature_scale(xt, t_val, w_rows, wsum, coll, F, True)
-        del t_indptr, t_idx, t_val, val64
-    else:
-        scale = _feature_scale(None, None, w_rows, wsum, coll, F, False)
-    hot_tables = (None, None)
-    if dev.type == "cuda":
-        hot_feat = nb_hot_set(indptr, idx, val, F, 1) if hot is None else \
-            torch.as_tensor(hot, dtype=torch.int32, device=dev).reshape(-1)
-        hot_tables = nb_hot_tables(hot_feat, F, 1)
+    coll, _, wsum, scale = weight_sum_and_scale(indptr, idx, val, F, w, n, standardization, "LinearSVC")
+    tables = hot_tables(indptr, idx, val, F, 1, hot)
     inv_k = math.ldexp(1.0, -k)
     lim = svc_limits()
     stats_ = SVC_STATS
@@ -109,12 +57,12 @@ def train_linear_svc(features, labels, weights=None, max_iter: int = 100, tol: f
         beta = theta[:F]
         # one copy per evaluation: the intercept travels as a kernel argument
         b = float(theta[F]) if fit_intercept else 0.0
-        res = svc_eval(indptr, idx, val, scale * beta, b, y, w, k, kl, hot_tables, chunk_rows=chunk_rows,
+        res = svc_eval(indptr, idx, val, scale * beta, b, y, w, k, kl, tables, chunk_rows=chunk_rows,
                        check_extents=stats_["evaluations"] == 0, threads=threads)
         block = coll.sum(res.block)
         gbq, lossq, nact, flag = (int(v) for v in block[F:].cpu())
         if flag >> 32:
-            _svc_raise(idx, val, y, w, F)
+            _raise_bad_input("svc", idx, val, y, w, F)
         first = stats_["evaluations"] == 0
         stats_["evaluations"] += 1
         stats_["active_share"] = nact / max(n_global, 1)

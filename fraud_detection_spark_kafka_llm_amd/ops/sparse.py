@@ -214,6 +214,16 @@ def nb_hot_tables(hot_feat: torch.Tensor, size: int, num_classes: int) -> tuple:
     return slot_of, hot_feat.to(torch.int32).contiguous()
 
 
+def hot_tables(indptr, idx, val, size: int, num_classes: int, hot=None) -> tuple:
+    """``nb_hot_tables`` of ``hot`` (feature ids; ``None`` = ``nb_hot_set``) for a CSR on a HIP device,
+    ``(None, None)`` on the host, which has no hot set."""
+    if indptr.device.type != "cuda":
+        return None, None
+    hot_feat = nb_hot_set(indptr, idx, val, size, num_classes) if hot is None else \
+        torch.as_tensor(hot, dtype=torch.int32, device=indptr.device).reshape(-1)
+    return nb_hot_tables(hot_feat, size, num_classes)
+
+
 def nb_sums(vc, labels, weights, num_classes: int, k: int, kw: int, bernoulli: bool = False, hot=None,
             threads: int = 0, chunk_rows: int = 0):
     """Exact class-conditional sums of a CSR column for Naive Bayes, ``(S [C, F], Wq [C], cnt [C])``
@@ -231,29 +241,35 @@ def nb_sums(vc, labels, weights, num_classes: int, k: int, kw: int, bernoulli: b
     dev, F = indptr.device, int(vc.size)
     y = torch.as_tensor(labels).to(device=dev, dtype=torch.float64).contiguous()
     w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
-    slot_of = hot_feat = None
-    if dev.type == "cuda":
-        hot_feat = nb_hot_set(indptr, idx, val, F, C_) if hot is None else \
-            torch.as_tensor(hot, dtype=torch.int32, device=dev).reshape(-1)
-        slot_of, hot_feat = nb_hot_tables(hot_feat, F, C_)
+    slot_of, hot_feat = hot_tables(indptr, idx, val, F, C_, hot)
     out = torch.zeros(C_ * F + 2 * C_ + 1, dtype=torch.int64, device=dev)
     native.lib().nb_sums(indptr, idx, val, y, w, C_, F, int(k), int(kw), bool(bernoulli), slot_of, hot_feat, out,
                          int(chunk_rows), threads)
     host = out.cpu()                                   # the flag travels with the sums
     if int(host[-1]):
-        _nb_raise(idx, val, y, w, C_, F, bool(bernoulli))
+        _raise_bad_input("nb", idx, val, y, w, F, C_, bool(bernoulli))
     S = host[:C_ * F].view(C_, F)
     return S, host[C_ * F:C_ * F + C_], host[C_ * F + C_:C_ * F + 2 * C_]
 
 
-def _nb_raise(idx, val, y, w, C_: int, F: int, bernoulli: bool) -> None:
-    """Name the bad input behind the pass's flag word (the slow path: only taken on an error)."""
-    if not bool(torch.all((y >= 0) & (y < C_) & (y == torch.floor(y)))):
-        raise ValueError(f"Naive Bayes labels must be integers in 0 .. {C_ - 1}")
-    if w is not None and not bool(torch.all(torch.isfinite(w) & (w > 0))):
-        raise ValueError("Naive Bayes weights must be finite and > 0")
+# family -> (its name in messages, whether a weight may be 0)
+_FAMILIES = {"nb": ("Naive Bayes", False), "mlr": ("multinomial logistic regression", True),
+             "svc": ("LinearSVC", True)}
+
+
+def _raise_bad_input(family: str, idx, val, y, w, F: int, C_: Optional[int] = None, bernoulli: bool = False) -> None:
+    """Name the bad input behind a pass's flag word (the slow path: only taken on an error). Labels
+    are integers in ``0 .. C_ - 1``, or 0 / 1 where ``C_`` is ``None``."""
+    name, zero_ok = _FAMILIES[family]
+    labels_ok = (y == 0) | (y == 1) if C_ is None else (y >= 0) & (y < C_) & (y == torch.floor(y))
+    if not bool(torch.all(labels_ok)):
+        raise ValueError(f"{name} labels must be " + ("0 or 1" if C_ is None else f"integers in 0 .. {C_ - 1}"))
+    if w is not None and not bool(torch.all(torch.isfinite(w) & ((w >= 0) if zero_ok else (w > 0)))):
+        raise ValueError(f"{name} weights must be finite and " + (">= 0" if zero_ok else "> 0"))
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
         raise ValueError("feature index outside the feature space")
+    if family != "nb":
+        raise ValueError(f"{name} requires finite feature values")
     if bernoulli:
         raise ValueError("Bernoulli Naive Bayes requires feature values 0 or 1")
     raise ValueError("Multinomial Naive Bayes requires finite, non-negative feature values")
@@ -287,8 +303,26 @@ def mlr_scale_exponents(wmax: float, vmax: float, n_rows: int) -> tuple:
     return k, kl
 
 
+class _FlaggedBlock:
+    """An int64 block whose last word is the flag word of ``csrc/fixedpoint.h``: the low half says
+    that a row's loss was clamped, the high half names bad input."""
+    block: torch.Tensor
+
+    @property
+    def flag(self) -> int:
+        return int(self.block[-1])
+
+    @property
+    def clamped(self) -> bool:
+        return bool(self.flag & 0xFFFFFFFF)
+
+    @property
+    def bad_input(self) -> bool:
+        return bool(self.flag >> 32)
+
+
 @dataclass
-class MlrBlock:
+class MlrBlock(_FlaggedBlock):
     """The int64 block of one ``mlr_eval``: ``Gq`` [F, C] feature-major, ``gbq`` [C], ``lossq``, the
     two flags, and the per-row outputs when they were asked for."""
     block: torch.Tensor
@@ -309,14 +343,6 @@ class MlrBlock:
     @property
     def lossq(self) -> int:
         return int(self.block[-2])
-
-    @property
-    def clamped(self) -> bool:
-        return bool(int(self.block[-1]) & 0xFFFFFFFF)
-
-    @property
-    def bad_input(self) -> bool:
-        return bool(int(self.block[-1]) >> 32)
 
 
 def mlr_eval(indptr, idx, val, XS: torch.Tensor, b: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor],
@@ -350,7 +376,7 @@ def svc_limits() -> dict:
 
 
 @dataclass
-class SvcBlock:
+class SvcBlock(_FlaggedBlock):
     """The int64 block of one ``svc_eval``: ``Gq`` [F], ``gbq``, ``lossq``, ``nact``, the flag word,
     and the per-row outputs when they were asked for."""
     block: torch.Tensor
@@ -374,18 +400,6 @@ class SvcBlock:
     @property
     def nact(self) -> int:
         return int(self.block[self.F + 2])
-
-    @property
-    def flag(self) -> int:
-        return int(self.block[self.F + 3])
-
-    @property
-    def clamped(self) -> bool:
-        return bool(self.flag & 0xFFFFFFFF)
-
-    @property
-    def bad_input(self) -> bool:
-        return bool(self.flag >> 32)
 
 
 def svc_eval(indptr, idx, val, xs: torch.Tensor, b: float, y: torch.Tensor, w: Optional[torch.Tensor],

@@ -299,7 +299,7 @@ def test_limits():
 
 
 def test_sanitized_host_twin_selftest():
-    exe = _build.build_contrib_selftest(sanitize=True)
+    exe = _build.build_selftest("contrib", sanitize=True)
     res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
                          timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr

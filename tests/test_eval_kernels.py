@@ -125,7 +125,7 @@ def test_sums_do_not_depend_on_the_thread_count():
 
 
 def test_sanitized_host_twin_selftest():
-    exe = _build.build_eval_selftest(sanitize=True)
+    exe = _build.build_selftest("eval", sanitize=True)
     res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
                          timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr

@@ -512,7 +512,7 @@ def test_fit_is_bitwise_repeatable(device):
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
                     reason="needs hipcc")
 def test_lr_host_twins_clean_under_asan_ubsan():
-    exe = _build.build_lr_selftest(sanitize=True)
+    exe = _build.build_selftest("lr", sanitize=True)
     res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
                          timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr

@@ -532,7 +532,7 @@ def test_agent_names_bigrams(tmp_path):
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
                     reason="needs hipcc")
 def test_ngram_host_twin_clean_under_asan_ubsan():
-    exe = _build.build_ngram_selftest(sanitize=True)
+    exe = _build.build_selftest("ngram", sanitize=True)
     res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
                          timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr

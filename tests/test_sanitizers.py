@@ -13,7 +13,7 @@ from fraud_detection_spark_kafka_llm_amd import _build
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
                     reason="needs hipcc")
 def test_host_paths_clean_under_asan_ubsan():
-    exe = _build.build_host_selftest(sanitize=True)
+    exe = _build.build_selftest("host", sanitize=True)
     res = subprocess.run([str(exe)], env={**os.environ, **_build.SELFTEST_ENV}, capture_output=True, text=True,
                          timeout=300)
     assert res.returncode == 0, res.stdout + res.stderr
