@@ -727,6 +727,7 @@ void register_nb_ops(pybind11::module& m);
 void register_mlr_ops(pybind11::module& m);
 void register_svc_ops(pybind11::module& m);
 void register_softprob_ops(pybind11::module& m);
+void register_km_ops(pybind11::module& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native core of fraud_detection_spark_kafka_llm_amd";
@@ -740,6 +741,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_mlr_ops(m);
   register_svc_ops(m);
   register_softprob_ops(m);
+  register_km_ops(m);
   m.def("token_keys", &token_keys, "CountVectorizer fit: 64-bit token keys (count pass / key pass)");
   m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score",
         py::arg("text"), py::arg("doc_off"), py::arg("flags"), py::arg("num_features"), py::arg("stop"),

@@ -84,10 +84,11 @@ struct FxLaunch {
   size_t lds;                // bytes of the hot table
 };
 
-// classes = 1 for a model without classes (SVC)
-inline FxLaunch fx_launch(const char* op, int classes, int min_classes, const HotSet& h, int64_t rows) {
-  if (classes < min_classes || classes > kNbMaxClasses || h.chunk_rows < 1 || h.hot_slots < 0 ||
-      (int64_t)classes * h.hot_slots * 8 > kNbMaxTableBytes)
+// classes = 1 for a model without classes (SVC); KMeans raises the class cap and lowers the table's
+inline FxLaunch fx_launch(const char* op, int classes, int min_classes, const HotSet& h, int64_t rows,
+                          int max_classes = kNbMaxClasses, int max_table_bytes = kNbMaxTableBytes) {
+  if (classes < min_classes || classes > max_classes || h.chunk_rows < 1 || h.hot_slots < 0 ||
+      (int64_t)classes * h.hot_slots * 8 > max_table_bytes)
     throw std::runtime_error(std::string("fdx ") + op + ": classes, chunk or hot set out of range");
   return {(unsigned)nb_chunks(rows, h.chunk_rows), (size_t)classes * h.hot_slots * sizeof(uint64_t)};
 }

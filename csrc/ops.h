@@ -93,6 +93,16 @@ template <class V> void nb_sums_cpu(const NbSumArgs<V>& a, int threads);
 template <class V> void launch_nb_score(const NbScoreArgs<V>& a, hipStream_t stream);
 template <class V> void nb_score_cpu(const NbScoreArgs<V>& a, int threads);
 
+// ---------------------------------------------------------------- KMeans (km_kernels.hip / km_cpu.cpp)
+template <class V> struct KmStepArgs;   // km.h
+struct KmCentersArgs;
+// one Lloyd evaluation: assignments and exact int64 sums (any grid, chunk, hot set or thread count gives the same bits)
+template <class V> void launch_km_step(const KmStepArgs<V>& a, hipStream_t stream);
+template <class V> void km_step_cpu(const KmStepArgs<V>& a, int threads);
+// centers, squared norms and squared moves from the sums, in a summation order fixed by F
+void launch_km_centers(const KmCentersArgs& a, hipStream_t stream);
+void km_centers_cpu(const KmCentersArgs& a, int threads);
+
 // ---------------------------------------------------------------- feature-major order (sort_kernels.hip)
 template <class V>
 struct FeatureOrderArgs {

@@ -155,6 +155,7 @@ SELFTESTS = {
     "mlr": (("nb_cpu.cpp", "mlr_cpu.cpp"), "multinomial logistic-regression host twin"),
     "softprob": (("softprob_cpu.cpp",), "multi-class boosting host twins"),
     "svc": (("svc_cpu.cpp",), "linear SVC host twin"),
+    "km": (("km_cpu.cpp",), "KMeans host twins"),
 }
 
 

@@ -3,6 +3,7 @@ from .base import Estimator, Model, Param, Params, Pipeline, PipelineModel, Tran
 from .classification import (DecisionTreeClassificationModel, DecisionTreeClassifier, LinearSVC, LinearSVCModel,
                              LogisticRegression, LogisticRegressionModel, NaiveBayes, NaiveBayesModel,
                              RandomForestClassificationModel, RandomForestClassifier)
+from .clustering import KMeans, KMeansModel, KMeansSummary
 from .feature import (IDF, CountVectorizer, CountVectorizerModel, HashingTF, IDFModel, NGram, StopWordsRemover,
                       Tokenizer)
 from .frame import Frame, Row, TextColumn, TokenColumn

@@ -52,6 +52,9 @@ class FusedPipeline:
     @classmethod
     def from_stages(cls, stages: Sequence, device=None, multiclass: bool = False) -> "FusedPipeline":
         chain = match_chain(stages)
+        if stages and type(stages[-1]).__name__ == "KMeansModel":
+            raise NotImplementedError("a pipeline that ends in a KMeansModel does not compile: the fused launch has no "
+                                      "assign tail (transform takes the staged route over ops.sparse.km_step)")
         if chain is None or chain[-1] != len(stages):
             raise ValueError("pipeline is not a fusable text->classifier chain")
         return cls(*chain[:6], device=device, multiclass=multiclass)

@@ -254,25 +254,163 @@ def nb_sums(vc, labels, weights, num_classes: int, k: int, kw: int, bernoulli: b
 
 # family -> (its name in messages, whether a weight may be 0)
 _FAMILIES = {"nb": ("Naive Bayes", False), "mlr": ("multinomial logistic regression", True),
-             "svc": ("LinearSVC", True)}
+             "svc": ("LinearSVC", True), "km": ("KMeans", False)}
 
 
 def _raise_bad_input(family: str, idx, val, y, w, F: int, C_: Optional[int] = None, bernoulli: bool = False) -> None:
     """Name the bad input behind a pass's flag word (the slow path: only taken on an error). Labels
-    are integers in ``0 .. C_ - 1``, or 0 / 1 where ``C_`` is ``None``."""
+    are integers in ``0 .. C_ - 1``, or 0 / 1 where ``C_`` is ``None``; ``y`` is ``None`` for a family
+    without labels (KMeans)."""
     name, zero_ok = _FAMILIES[family]
-    labels_ok = (y == 0) | (y == 1) if C_ is None else (y >= 0) & (y < C_) & (y == torch.floor(y))
-    if not bool(torch.all(labels_ok)):
+    labels_ok = None if y is None else \
+        (y == 0) | (y == 1) if C_ is None else (y >= 0) & (y < C_) & (y == torch.floor(y))
+    if labels_ok is not None and not bool(torch.all(labels_ok)):
         raise ValueError(f"{name} labels must be " + ("0 or 1" if C_ is None else f"integers in 0 .. {C_ - 1}"))
     if w is not None and not bool(torch.all(torch.isfinite(w) & ((w >= 0) if zero_ok else (w > 0)))):
         raise ValueError(f"{name} weights must be finite and " + (">= 0" if zero_ok else "> 0"))
     if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
         raise ValueError("feature index outside the feature space")
+    if family == "km" and bool(torch.all(torch.isfinite(val))):
+        raise ValueError("KMeans requires rows of a finite norm that is not zero under the cosine measure")
     if family != "nb":
         raise ValueError(f"{name} requires finite feature values")
     if bernoulli:
         raise ValueError("Bernoulli Naive Bayes requires feature values 0 or 1")
     raise ValueError("Multinomial Naive Bayes requires finite, non-negative feature values")
+
+
+# ---------------------------------------------------------------------------------------------- KMeans
+KM_MEASURES = {"euclidean": 0, "cosine": 1}
+
+
+def km_limits() -> dict:
+    """Structural constants of the KMeans kernels: ``max_k``, the centers of a register ``tile``, the
+    width of ``km_centers``' summation tree (``centers_block``) and those of ``nb_limits`` it shares
+    (``chunk_rows``, ``table_bytes``, ``k_max``, ``sum_bits``, ``prefix_rows``, wave and workgroup
+    size); ``max_table_bytes`` is its own, the table shares the workgroup with ``2 max_k + 1`` sums."""
+    return dict(native.lib().km_limits())
+
+
+def km_padded(K: int) -> int:
+    """``Kp``: ``K`` rounded up to the tile."""
+    tile = int(km_limits()["tile"])
+    return (int(K) + tile - 1) // tile * tile
+
+
+def _km_check(name: str, K: int, measure: str) -> int:
+    lim = km_limits()
+    if not 2 <= int(K) <= lim["max_k"]:
+        raise ValueError(f"{name}: KMeans passes take 2 .. {lim['max_k']} centers, got {K}")
+    if measure not in KM_MEASURES:
+        raise ValueError(f"{name}: unknown distance measure {measure!r} (euclidean, cosine)")
+    return KM_MEASURES[measure]
+
+
+@dataclass
+class KmBlock:
+    """The int64 block of one ``km_step``: ``S`` [K, F] (``None`` for an assign-only pass), ``Wq`` [K],
+    ``cnt`` [K], ``costq``, the flag word, and the per-row outputs when they were asked for. The block
+    stays on the CSR's device."""
+    block: torch.Tensor
+    F: int
+    K: int
+    sums: bool
+    assign: Optional[torch.Tensor] = None
+    dist: Optional[torch.Tensor] = None
+
+    @property
+    def _base(self) -> int:
+        return self.K * self.F if self.sums else 0
+
+    @property
+    def S(self) -> Optional[torch.Tensor]:
+        return self.block[:self._base].view(self.K, self.F) if self.sums else None
+
+    @property
+    def Wq(self) -> torch.Tensor:
+        return self.block[self._base:self._base + self.K]
+
+    @property
+    def cnt(self) -> torch.Tensor:
+        return self.block[self._base + self.K:self._base + 2 * self.K]
+
+    @property
+    def costq(self) -> int:
+        return int(self.block[-2])
+
+    @property
+    def flag(self) -> int:
+        return int(self.block[-1])
+
+
+def km_step(vc, CT: torch.Tensor, cn: torch.Tensor, K: int, measure: str, k: int, kw: int, kc: int, weights=None,
+            hot=None, sums: bool = True, want_rows: bool = False, chunk_rows: int = 0, threads: int = 0,
+            check: bool = True) -> KmBlock:
+    """One Lloyd evaluation of a CSR column against ``K`` centers (``CT`` [F, Kp] fp64 feature-major,
+    padding columns zero; ``cn`` [Kp] their squared norms) in one fused pass: every row's distances
+    (dots and the squared norm in spmv's order), its cluster ``a`` (the smallest index that attains
+    the least distance) and the exact int64 sums ``S[a, f] += rint(s x 2^k)`` (``s = w``, cosine:
+    ``w / |x|``), ``Wq[a] += rint(w 2^kw)``, ``cnt[a] += 1``, ``costq += rint(w d_a 2^kc)``.
+    ``sums=False`` skips ``S`` (assign only); ``want_rows`` adds ``assign`` int32 and ``dist`` fp64 per
+    row. Integer sums do not depend on order: ``hot`` (device: feature ids accumulated in LDS; ``None``
+    = ``nb_hot_set``, empty = every entry goes to a global atomic; a pair is taken as ready
+    ``nb_hot_tables``), ``chunk_rows`` and ``threads`` change the speed only. Raises ``ValueError``
+    before any launch for ``K`` outside ``2 .. max_k``, an unknown measure or a shape mismatch, and
+    with ``check`` after the pass for bad input (a feature id outside the space, a value or a row norm
+    that is not finite, a weight that is not finite and > 0, a zero row under cosine); without
+    ``check`` the caller tests ``flag``."""
+    m = _km_check("km_step", K, measure)
+    lim = km_limits()
+    K, Kp = int(K), km_padded(K)
+    indptr, idx, val = _csr(vc)
+    dev, F, n = indptr.device, int(vc.size), indptr.numel() - 1
+    if CT.dtype != torch.float64 or CT.dim() != 2 or tuple(CT.shape) != (F, Kp) or CT.device != dev:
+        raise ValueError(f"km_step: CT is float64 [{F}, {Kp}] on the CSR's device")
+    if cn.dtype != torch.float64 or cn.numel() != Kp or cn.device != dev:
+        raise ValueError(f"km_step: cn is float64 [{Kp}] on the CSR's device")
+    if not all(0 <= int(e) <= lim["k_max"] for e in (k, kw, kc)):
+        raise ValueError(f"km_step: scale exponents lie in 0 .. {lim['k_max']}")
+    w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+    if w is not None and w.numel() != n:
+        raise ValueError("km_step: weights needs one entry per row")
+    slot_of = hot_feat = None
+    if sums and dev.type == "cuda":
+        slot_of, hot_feat = hot if isinstance(hot, tuple) else hot_tables(indptr, idx, val, F, K, hot)
+        if hot_feat is not None and hot_feat.numel() * 8 * K > lim["max_table_bytes"]:
+            raise ValueError("km_step: the hot set exceeds the LDS table")
+    out = torch.zeros((K * F if sums else 0) + 2 * K + 2, dtype=torch.int64, device=dev)
+    assign = torch.empty(n, dtype=torch.int32, device=dev) if want_rows else None
+    dist = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    native.lib().km_step(indptr, idx, val, w, CT.contiguous(), cn.contiguous(), K, m, int(k), int(kw), int(kc),
+                         slot_of, hot_feat, out, bool(sums), assign, dist, int(chunk_rows), threads)
+    blk = KmBlock(out, F, K, bool(sums), assign, dist)
+    if check and blk.flag:
+        _raise_bad_input("km", idx, val, None, w, F)
+    return blk
+
+
+def km_centers(S: torch.Tensor, Wq: torch.Tensor, CT_old: torch.Tensor, K: int, k: int, kw: int, measure: str,
+               threads: int = 0) -> tuple:
+    """The update of a Lloyd iteration on the sums' device, ``(CT [F, Kp], cn [Kp], moved2 [K])``:
+    ``center_c = S[c] 2^-k / (Wq[c] 2^-kw)`` (cosine: divided by its norm), a cluster with ``Wq[c] = 0``
+    keeps its center; ``cn`` the squared norms and ``moved2`` the squared moves, every sum over the
+    features in an order that depends on ``F`` alone (bitwise equal on host and device). Raises
+    ``ValueError`` before any launch for ``K`` outside ``2 .. max_k``, an unknown measure or a shape
+    mismatch."""
+    m = _km_check("km_centers", K, measure)
+    K, Kp = int(K), km_padded(K)
+    dev = S.device
+    if CT_old.dim() != 2 or CT_old.shape[1] != Kp or CT_old.dtype != torch.float64 or CT_old.device != dev:
+        raise ValueError(f"km_centers: CT_old is float64 [F, {Kp}] on the sums' device")
+    F = int(CT_old.shape[0])
+    if S.dtype != torch.int64 or S.numel() != K * F or Wq.dtype != torch.int64 or Wq.numel() != K or Wq.device != dev:
+        raise ValueError(f"km_centers: S is int64 [{K}, {F}], Wq int64 [{K}]")
+    CT = torch.zeros((F, Kp), dtype=torch.float64, device=dev)
+    cn = torch.zeros(Kp, dtype=torch.float64, device=dev)
+    moved2 = torch.zeros(K, dtype=torch.float64, device=dev)
+    native.lib().km_centers(S.contiguous(), Wq.contiguous(), CT_old.contiguous(), K, int(k), int(kw), m, CT, cn, moved2,
+                            threads)
+    return CT, cn, moved2
 
 
 def mlr_limits() -> dict:

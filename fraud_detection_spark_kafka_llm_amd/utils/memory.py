@@ -129,6 +129,17 @@ def validation_bytes(n_val: int, val_nnz: int = 0) -> float:
     return VAL_ENTRY_BYTES * max(int(val_nnz), 0) + VAL_ROW_BYTES * int(n_val)
 
 
+def kmeans_bytes(rows: int, nnz: int, k: int, num_features: int, value_bytes: int = 8) -> float:
+    """Peak bytes of a KMeans fit (models/kmeans.py) on one shard of ``rows`` rows with ``nnz`` entries:
+    the CSR, the sums ``S`` (``8 K F``), the centers ``CT`` before and after the update (``8 Kp F``
+    twice, ``Kp`` = ``K`` rounded up to 8), the 2-byte slot table of the hot set and the per-row outputs
+    of a seeding pass (int32 cluster, fp64 distance, and the running minimum and index of k-means||)."""
+    kp = (int(k) + 7) // 8 * 8
+    per_row = 8.0 + 8.0 + (4.0 + 8.0) + (8.0 + 8.0)          # indptr, weight, assign + dist, running best
+    return (4.0 + value_bytes) * nnz + per_row * rows + 8.0 * int(k) * num_features + 2 * 8.0 * kp * num_features \
+        + 2.0 * num_features
+
+
 def rf_lanes_that_fit(rows: int, want: int, free_bytes: int, headroom: float = 0.5) -> int:
     """Trees in flight whose workspaces fit ``headroom`` of ``free_bytes`` (at least 1, at most
     ``want``): the cap models/tree.fit_forest applies before building its lanes."""
