@@ -439,9 +439,9 @@ void doc_freq(const Tensor& idx, const Tensor& val, const Tensor& df) {
   FDX_CHECK(idx.scalar_type() == at::kInt && df.scalar_type() == at::kLong, "indices i32 / df i64");
   c10::hip::HIPGuard guard(dev.index());
   if (val.scalar_type() == at::kFloat)
-    fdx::launch_doc_freq<float>(idx.data_ptr<int32_t>(), val.data_ptr<float>(), idx.numel(), df.data_ptr<int64_t>(), stream_of(dev));
+    fdx::launch_doc_freq<float>(idx.data_ptr<int32_t>(), val.data_ptr<float>(), idx.numel(), df.data_ptr<int64_t>(), df.numel(), stream_of(dev));
   else
-    fdx::launch_doc_freq<double>(idx.data_ptr<int32_t>(), val.data_ptr<double>(), idx.numel(), df.data_ptr<int64_t>(), stream_of(dev));
+    fdx::launch_doc_freq<double>(idx.data_ptr<int32_t>(), val.data_ptr<double>(), idx.numel(), df.data_ptr<int64_t>(), df.numel(), stream_of(dev));
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -728,6 +728,7 @@ void register_mlr_ops(pybind11::module& m);
 void register_svc_ops(pybind11::module& m);
 void register_softprob_ops(pybind11::module& m);
 void register_km_ops(pybind11::module& m);
+void register_clu_ops(pybind11::module& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native core of fraud_detection_spark_kafka_llm_amd";
@@ -742,6 +743,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_svc_ops(m);
   register_softprob_ops(m);
   register_km_ops(m);
+  register_clu_ops(m);
   m.def("token_keys", &token_keys, "CountVectorizer fit: 64-bit token keys (count pass / key pass)");
   m.def("featurize_score", &featurize_score, "Fused clean/tokenize/stopword/hash/idf/score",
         py::arg("text"), py::arg("doc_off"), py::arg("flags"), py::arg("num_features"), py::arg("stop"),

@@ -39,7 +39,7 @@ template <class V> void launch_spmv(const int64_t* indptr, const int32_t* idx, c
 template <class V> void launch_spmv_t(const int64_t* indptr, const int32_t* idx, const V* val, const double* r,
                                      double* g, int64_t rows, hipStream_t stream);
 template <class V> void launch_doc_freq(const int32_t* idx, const V* val, int64_t nnz, int64_t* df,
-                                       hipStream_t stream);
+                                       int64_t size, hipStream_t stream);
 
 // ---------------------------------------------------------------- TreeSHAP (contrib_kernels.hip / contrib_cpu.cpp)
 template <class V> struct ContribArgs;   // contrib.h

@@ -89,11 +89,16 @@ __global__ __launch_bounds__(kBlock) void spmv_t_kernel(const int64_t* indptr, c
     atomicAdd(&g[idx[j]], (double)val[j] * rr);
 }
 
-// docFreq[f] += 1 for every stored non-zero (IDF fit, X-06).
+// docFreq[f] += 1 for every stored non-zero (IDF fit, X-06). An id outside 0 .. size - 1 is skipped: the
+// hot set of a fixed-point pass is chosen before that pass has validated (and flagged) the ids.
 template <class V>
-__global__ __launch_bounds__(kBlock) void doc_freq_kernel(const int32_t* idx, const V* val, int64_t nnz, int64_t* df) {
-  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < nnz; j += (int64_t)gridDim.x * kBlock)
-    if (val[j] != (V)0) atomicAdd(reinterpret_cast<unsigned long long*>(&df[idx[j]]), 1ull);
+__global__ __launch_bounds__(kBlock) void doc_freq_kernel(const int32_t* idx, const V* val, int64_t nnz, int64_t* df,
+                                                          int64_t size) {
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < nnz; j += (int64_t)gridDim.x * kBlock) {
+    const int32_t f = idx[j];
+    if ((uint64_t)(int64_t)f < (uint64_t)size && val[j] != (V)0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(&df[f]), 1ull);
+  }
 }
 
 inline dim3 row_grid(int64_t rows) { return dim3((unsigned)((rows + (kBlock / kWave) - 1) / (kBlock / kWave))); }
@@ -126,13 +131,13 @@ template void launch_spmv_t<float>(const int64_t*, const int32_t*, const float*,
 template void launch_spmv_t<double>(const int64_t*, const int32_t*, const double*, const double*, double*, int64_t, hipStream_t);
 
 template <class V>
-void launch_doc_freq(const int32_t* idx, const V* val, int64_t nnz, int64_t* df, hipStream_t stream) {
+void launch_doc_freq(const int32_t* idx, const V* val, int64_t nnz, int64_t* df, int64_t size, hipStream_t stream) {
   if (nnz <= 0) return;
   const int64_t want = (nnz + kBlock - 1) / kBlock;
   const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
-  hipLaunchKernelGGL(doc_freq_kernel<V>, dim3(grid), dim3(kBlock), 0, stream, idx, val, nnz, df);
+  hipLaunchKernelGGL(doc_freq_kernel<V>, dim3(grid), dim3(kBlock), 0, stream, idx, val, nnz, df, size);
 }
-template void launch_doc_freq<float>(const int32_t*, const float*, int64_t, int64_t*, hipStream_t);
-template void launch_doc_freq<double>(const int32_t*, const double*, int64_t, int64_t*, hipStream_t);
+template void launch_doc_freq<float>(const int32_t*, const float*, int64_t, int64_t*, int64_t, hipStream_t);
+template void launch_doc_freq<double>(const int32_t*, const double*, int64_t, int64_t*, int64_t, hipStream_t);
 
 }  // namespace fdx

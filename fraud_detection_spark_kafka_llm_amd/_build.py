@@ -156,6 +156,7 @@ SELFTESTS = {
     "softprob": (("softprob_cpu.cpp",), "multi-class boosting host twins"),
     "svc": (("svc_cpu.cpp",), "linear SVC host twin"),
     "km": (("km_cpu.cpp",), "KMeans host twins"),
+    "clu": (("clu_cpu.cpp",), "bisecting KMeans and silhouette host twins"),
 }
 
 

@@ -3,7 +3,9 @@ from .base import Estimator, Model, Param, Params, Pipeline, PipelineModel, Tran
 from .classification import (DecisionTreeClassificationModel, DecisionTreeClassifier, LinearSVC, LinearSVCModel,
                              LogisticRegression, LogisticRegressionModel, NaiveBayes, NaiveBayesModel,
                              RandomForestClassificationModel, RandomForestClassifier)
-from .clustering import KMeans, KMeansModel, KMeansSummary
+from .clustering import (BisectingKMeans, BisectingKMeansModel, BisectingKMeansSummary, KMeans, KMeansModel,
+                         KMeansSummary)
+from .evaluation import ClusteringEvaluator
 from .feature import (IDF, CountVectorizer, CountVectorizerModel, HashingTF, IDFModel, NGram, StopWordsRemover,
                       Tokenizer)
 from .frame import Frame, Row, TextColumn, TokenColumn

@@ -196,6 +196,35 @@ class MulticlassClassificationEvaluator(Params):
                                             "logLoss")
 
 
+class ClusteringEvaluator(Params):
+    """Spark's ``ClusteringEvaluator``: the silhouette of ``predictionCol`` over ``featuresCol``, two exact
+    passes over the CSR (``models/silhouette.py``). Host, device and every world size of the ambient
+    process group give the same value bit for bit."""
+    _uid_prefix = "ClusteringEvaluator"
+    _java_class = "org.apache.spark.ml.evaluation.ClusteringEvaluator"
+    _params = [Param("predictionCol", "prediction column", "prediction", str),
+               Param("featuresCol", "features column", "features", str),
+               Param("metricName", "silhouette", "silhouette", str),
+               Param("distanceMeasure", "squaredEuclidean|cosine", "squaredEuclidean", str),
+               Param("weightCol", "weight column", None, str, has_default=False)]
+
+    def evaluate(self, frame: Frame, params: Optional[dict] = None) -> float:
+        from ..models.silhouette import silhouette
+
+        ev = self.copy(params) if params else self
+        if ev.getMetricName() != "silhouette":
+            raise ValueError(f"unknown ClusteringEvaluator metricName {ev.getMetricName()!r} (silhouette)")
+        if ev.getDistanceMeasure() not in ("squaredEuclidean", "cosine"):
+            raise ValueError(f"unknown ClusteringEvaluator distanceMeasure {ev.getDistanceMeasure()!r} "
+                             "(squaredEuclidean, cosine)")
+        w = frame.column(ev.getWeightCol()) if ev.isSet("weightCol") else None
+        return silhouette(frame.column(ev.getFeaturesCol()), frame.column(ev.getPredictionCol()), w,
+                          ev.getDistanceMeasure())["value"]
+
+    def isLargerBetter(self) -> bool:  # noqa: N802
+        return True
+
+
 def evaluate_all(frame: Frame, label_col: str = "labels") -> dict:
     """The reference's metric set (fraud_detection_spark.py:101-123) in one device pass."""
     y = _labels(frame.column(label_col))

@@ -55,6 +55,10 @@ class FusedPipeline:
         if stages and type(stages[-1]).__name__ == "KMeansModel":
             raise NotImplementedError("a pipeline that ends in a KMeansModel does not compile: the fused launch has no "
                                       "assign tail (transform takes the staged route over ops.sparse.km_step)")
+        if stages and type(stages[-1]).__name__ == "BisectingKMeansModel":
+            raise NotImplementedError("a pipeline that ends in a BisectingKMeansModel does not compile: the fused launch "
+                                      "has no assign tail (transform takes the staged route over "
+                                      "ops.sparse.km_group_step)")
         if chain is None or chain[-1] != len(stages):
             raise ValueError("pipeline is not a fusable text->classifier chain")
         return cls(*chain[:6], device=device, multiclass=multiclass)

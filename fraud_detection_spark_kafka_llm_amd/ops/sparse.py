@@ -413,6 +413,194 @@ def km_centers(S: torch.Tensor, Wq: torch.Tensor, CT_old: torch.Tensor, K: int, 
     return CT, cn, moved2
 
 
+# ---------------------------------------------------------------------------------------------- bisecting / silhouette
+def clu_limits() -> dict:
+    """Structural constants of ``km_group_step`` and ``sil_score``: ``max_k``, ``max_width`` (the
+    candidates of a row), the ``tile`` and those of ``km_limits`` they share (``chunk_rows``,
+    ``table_bytes``, ``max_table_bytes``, ``k_max``, ``sum_bits``, wave and workgroup size)."""
+    return dict(native.lib().clu_limits())
+
+
+def _clu_measure(name: str, measure: str) -> int:
+    if measure not in KM_MEASURES:
+        raise ValueError(f"{name}: unknown distance measure {measure!r} (euclidean, cosine)")
+    return KM_MEASURES[measure]
+
+
+def _clu_rows(name: str, what: str, t, n: int, dev) -> torch.Tensor:
+    """An int32 entry per row on the CSR's device."""
+    t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.numel() != n:
+        raise ValueError(f"{name}: {what} is an integer per row")
+    return t.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+
+
+@dataclass
+class KmGroupBlock:
+    """The int64 block of one ``km_group_step``: ``S`` [K, F] (``None`` for an assign-only pass), ``Wq``
+    [K], ``cnt`` [K], ``costq`` [K] (per cluster), the flag word, and the per-row outputs when they
+    were asked for. The block stays on the CSR's device."""
+    block: torch.Tensor
+    F: int
+    K: int
+    sums: bool
+    assign: Optional[torch.Tensor] = None
+    dist: Optional[torch.Tensor] = None
+
+    @property
+    def _base(self) -> int:
+        return self.K * self.F if self.sums else 0
+
+    @property
+    def S(self) -> Optional[torch.Tensor]:
+        return self.block[:self._base].view(self.K, self.F) if self.sums else None
+
+    @property
+    def Wq(self) -> torch.Tensor:
+        return self.block[self._base:self._base + self.K]
+
+    @property
+    def cnt(self) -> torch.Tensor:
+        return self.block[self._base + self.K:self._base + 2 * self.K]
+
+    @property
+    def costq(self) -> torch.Tensor:
+        return self.block[self._base + 2 * self.K:self._base + 3 * self.K]
+
+    @property
+    def flag(self) -> int:
+        return int(self.block[-1])
+
+
+def km_group_step(vc, group, W: int, G: int, CT: torch.Tensor, cn: torch.Tensor, measure: str, k: int, kw: int,
+                  kc: int, weights=None, hot=None, sums: bool = True, want_rows: bool = False, chunk_rows: int = 0,
+                  threads: int = 0, check: bool = True) -> KmGroupBlock:
+    """A Lloyd step in which the caller names each row's candidates: row ``r`` with ``g = group[r]``
+    competes among the ``W`` (1 or 2) adjacent centers ``W g .. W g + W - 1`` of ``CT`` [F, Kp] (``K =
+    max(2, W G) <= max_k``, ``Kp = km_padded(K)``, ``cn`` [Kp] the squared norms). ``g < 0`` skips the row:
+    only ``group[r]`` is read, nothing is added, ``assign = -1`` and ``dist = 0``. One walk in spmv's
+    order gives the squared norm and the dots, ``d_i = km_distance``, the left child wins ties, and
+    the exact int64 sums go to the cluster ``c = W g + a``: ``S[c, f] += rint(s x 2^k)``, ``Wq[c] +=
+    rint(w 2^kw)``, ``cnt[c] += 1`` and the per-cluster ``costq[c] += rint(w d 2^kc)``. ``sums``,
+    ``want_rows``, ``hot``, ``chunk_rows``, ``threads`` and ``check`` as in ``km_step``: they change no
+    bit. Raises ``ValueError`` before any launch for a width outside 1 .. 2, ``W G > max_k``, an
+    unknown measure or a shape mismatch, and with ``check`` after the pass for bad input
+    (``km_step``'s cases and a group ``>= G``)."""
+    name = "km_group_step"
+    lim = clu_limits()
+    W, G = int(W), int(G)
+    if W not in (1, 2) or G < 1 or W * G > lim["max_k"]:
+        raise ValueError(f"{name}: the width is 1 or 2 and width * groups at most {lim['max_k']}, got {W} x {G}")
+    m = _clu_measure(name, measure)
+    K = max(2, W * G)
+    Kp = km_padded(K)
+    indptr, idx, val = _csr(vc)
+    dev, F, n = indptr.device, int(vc.size), indptr.numel() - 1
+    if CT.dtype != torch.float64 or CT.dim() != 2 or tuple(CT.shape) != (F, Kp) or CT.device != dev:
+        raise ValueError(f"{name}: CT is float64 [{F}, {Kp}] on the CSR's device")
+    if cn.dtype != torch.float64 or cn.numel() != Kp or cn.device != dev:
+        raise ValueError(f"{name}: cn is float64 [{Kp}] on the CSR's device")
+    if not all(0 <= int(e) <= lim["k_max"] for e in (k, kw, kc)):
+        raise ValueError(f"{name}: scale exponents lie in 0 .. {lim['k_max']}")
+    grp = _clu_rows(name, "group", group, n, dev)
+    w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+    if w is not None and w.numel() != n:
+        raise ValueError(f"{name}: weights needs one entry per row")
+    slot_of = hot_feat = None
+    if sums and dev.type == "cuda":
+        slot_of, hot_feat = hot if isinstance(hot, tuple) else hot_tables(indptr, idx, val, F, K, hot)
+        if hot_feat is not None and hot_feat.numel() * 8 * K > lim["max_table_bytes"]:
+            raise ValueError(f"{name}: the hot set exceeds the LDS table")
+    out = torch.zeros((K * F if sums else 0) + 3 * K + 1, dtype=torch.int64, device=dev)
+    assign = torch.empty(n, dtype=torch.int32, device=dev) if want_rows else None
+    dist = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    native.lib().km_group_step(indptr, idx, val, w, grp, W, G, CT.contiguous(), cn.contiguous(), m, int(k), int(kw),
+                               int(kc), slot_of, hot_feat, out, bool(sums), assign, dist, int(chunk_rows), threads)
+    blk = KmGroupBlock(out, F, K, bool(sums), assign, dist)
+    if check and blk.flag:
+        if bool(torch.any(grp >= G)):
+            raise ValueError(f"{name}: a group lies outside 0 .. {G - 1}")
+        live = grp >= 0                                   # a skipped row is not read, so it cannot be the bad one
+        entries = torch.repeat_interleave(live, indptr[1:] - indptr[:-1])
+        _raise_bad_input("km", idx[entries], val[entries], None, None if w is None else w[live], F)
+    return blk
+
+
+@dataclass
+class SilBlock:
+    """``[silq, wq, flag]`` of one ``sil_score`` on the CSR's device, and the per-row coefficients
+    when they were asked for."""
+    block: torch.Tensor
+    s: Optional[torch.Tensor] = None
+
+    @property
+    def silq(self) -> int:
+        return int(self.block[0])
+
+    @property
+    def wq(self) -> int:
+        return int(self.block[1])
+
+    @property
+    def flag(self) -> int:
+        return int(self.block[2])
+
+
+def sil_score(vc, labels, K: int, MT: torch.Tensor, psi: torch.Tensor, nw: torch.Tensor, cnt: torch.Tensor,
+              measure: str, ks: int, kw: int, weights=None, want_rows: bool = False, chunk_rows: int = 0,
+              threads: int = 0, check: bool = True) -> SilBlock:
+    """Spark's silhouette coefficient of every row, summed exactly. ``MT`` [F, Kp] fp64 are the
+    cluster means, feature-major (cosine: the means of the rows divided by their norms), ``psi`` [Kp]
+    (euclidean: the mean squared norm of a cluster's rows), ``nw`` [Kp] the weight sums (0 for an
+    absent cluster) and ``cnt`` [Kp] int32 the row counts. A row with the label ``a``: the dots and
+    the squared norm as in ``km_step`` (tiles of 8), ``D_c = (xn + psi_c) - 2 dot_c`` unclamped
+    (cosine: ``1 - dot_c / sqrt(xn)``), ``own = D_a nw_a / (nw_a - w)``, ``nb`` the least ``D_c`` over the
+    other present clusters (ascending, strict ``<``), ``s = 0`` for ``cnt_a == 1``, else ``1 - own / nb``,
+    ``nb / own - 1`` or 0; ``silq += rint(w s 2^ks)``, ``wq += rint(w 2^kw)``. ``want_rows`` adds ``s`` per
+    row. ``chunk_rows`` and ``threads`` change no bit. Raises ``ValueError`` before any launch for ``K``
+    outside ``2 .. max_k``, an unknown measure or a shape mismatch, and with ``check`` after the pass
+    for bad input: ``km_step``'s cases, a label outside ``0 .. K - 1`` or of an absent cluster, no other
+    present cluster, ``nw_a - w`` not > 0 for a non-singleton, or a coefficient that is not finite."""
+    name = "sil_score"
+    lim = clu_limits()
+    if not 2 <= int(K) <= lim["max_k"]:
+        raise ValueError(f"{name}: 2 .. {lim['max_k']} clusters, got {K}")
+    m = _clu_measure(name, measure)
+    K, Kp = int(K), km_padded(K)
+    indptr, idx, val = _csr(vc)
+    dev, F, n = indptr.device, int(vc.size), indptr.numel() - 1
+    if MT.dtype != torch.float64 or MT.dim() != 2 or tuple(MT.shape) != (F, Kp) or MT.device != dev:
+        raise ValueError(f"{name}: MT is float64 [{F}, {Kp}] on the CSR's device")
+    for what, t, dt in (("psi", psi, torch.float64), ("nw", nw, torch.float64), ("cnt", cnt, torch.int32)):
+        if t.dtype != dt or t.numel() != Kp or t.device != dev:
+            raise ValueError(f"{name}: {what} is {dt} [{Kp}] on the CSR's device")
+    if not all(0 <= int(e) <= lim["k_max"] for e in (ks, kw)):
+        raise ValueError(f"{name}: scale exponents lie in 0 .. {lim['k_max']}")
+    lab = _clu_rows(name, "labels", labels, n, dev)
+    w = None if weights is None else torch.as_tensor(weights).to(device=dev, dtype=torch.float64).contiguous()
+    if w is not None and w.numel() != n:
+        raise ValueError(f"{name}: weights needs one entry per row")
+    out = torch.zeros(3, dtype=torch.int64, device=dev)
+    s = torch.empty(n, dtype=torch.float64, device=dev) if want_rows else None
+    native.lib().sil_score(indptr, idx, val, w, lab, K, MT.contiguous(), psi.contiguous(), nw.contiguous(),
+                           cnt.contiguous(), m, int(ks), int(kw), out, s, int(chunk_rows), threads)
+    blk = SilBlock(out, s)
+    if check and blk.flag:
+        if bool(torch.any((lab < 0) | (lab >= K))):
+            raise ValueError(f"{name}: a label lies outside 0 .. {K - 1}")
+        if bool(torch.any(nw[lab.to(torch.int64)] <= 0)):
+            raise ValueError(f"{name}: a label names an absent cluster")
+        if int((nw[:K] > 0).sum()) < 2:
+            raise ValueError(f"{name}: the silhouette needs two clusters that are present")
+        norms = sim_norms(indptr, val)
+        if (w is not None and not bool(torch.all(torch.isfinite(w) & (w > 0)))) or not bool(torch.all(torch.isfinite(val))) \
+                or (idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F)) \
+                or not bool(torch.all(torch.isfinite(norms * norms))) or (m == 1 and bool(torch.any(norms == 0))):
+            _raise_bad_input("km", idx, val, None, w, F)
+        raise ValueError(f"{name}: a coefficient is not finite, or a cluster's weight sum does not exceed a row's")
+    return blk
+
+
 def mlr_limits() -> dict:
     """Structural constants of the multinomial logistic-regression kernel: those of ``nb_limits`` it
     shares (``max_classes``, ``chunk_rows``, ``table_bytes``, ``max_table_bytes``, ``k_max``,

@@ -200,28 +200,36 @@ def fit_softprob_xgb(feature_stages: list, label_col: str, datasets: dict, n_est
     return out
 
 
-def fit_kmeans_clusters(feature_stages: list, k: int, train_df: Frame, path: str, seed: int) -> dict:
-    """``KMeans(k)`` on the fitted feature stages' TF-IDF features of ``train_df``: prints the cluster
-    sizes and the scam share per cluster and saves the model to ``path``."""
-    from .ml import KMeans
+def fit_kmeans_clusters(feature_stages: list, k: int, train_df: Frame, path: str, seed: int, bisecting: bool = False,
+                        silhouette: bool = False) -> dict:
+    """``KMeans(k)`` (``bisecting``: ``BisectingKMeans(k)``) on the fitted feature stages' TF-IDF features of
+    ``train_df``: prints the cluster sizes and the scam share per cluster, with ``silhouette`` the
+    ``ClusteringEvaluator`` value too, and saves the model to ``path``."""
+    from .ml import BisectingKMeans, ClusteringEvaluator, KMeans
 
     cur = train_df
     for s in feature_stages:
         cur = s.transform(cur)
-    model = KMeans(featuresCol="features", k=int(k), seed=int(seed)).fit(cur)
-    pred = model.transform(cur).column("prediction")
+    name = "BisectingKMeans" if bisecting else "KMeans"
+    model = (BisectingKMeans if bisecting else KMeans)(featuresCol="features", k=int(k), seed=int(seed)).fit(cur)
+    out = model.transform(cur)
+    pred = out.column("prediction")
     pred = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
     y = np.asarray(train_df.column("labels"), dtype=np.float64)
     sizes = np.bincount(pred, minlength=model.summary.k)
     share = [float(y[pred == c].mean()) if sizes[c] else 0.0 for c in range(model.summary.k)]
-    print(f"\nKMeans (k = {model.summary.k}, {model.summary.numIter} iterations, cost {model.summary.trainingCost:.4f}):")
+    print(f"\n{name} (k = {model.summary.k}, {model.summary.numIter} iterations, cost {model.summary.trainingCost:.4f}):")
     for c in range(model.summary.k):
         print(f"cluster {c}: {int(sizes[c])} dialogues, scam share {share[c]:.3f}")
+    res = {"k": model.summary.k, "numIter": model.summary.numIter, "trainingCost": model.summary.trainingCost,
+           "clusterSizes": [int(v) for v in sizes], "scamShare": share, "path": path}
+    if silhouette:
+        res["silhouette"] = ClusteringEvaluator(featuresCol="features").evaluate(out)
+        print(f"silhouette {res['silhouette']:.4f}")
     if os.path.exists(path):
         shutil.rmtree(path)
     model.save(path)
-    return {"k": model.summary.k, "numIter": model.summary.numIter, "trainingCost": model.summary.trainingCost,
-            "clusterSizes": [int(v) for v in sizes], "scamShare": share, "path": path}
+    return res
 
 
 def analyze_word_associations(spark, model: PipelineModel, df: Frame, vocab: list, top_n: int = 10) -> Optional[Frame]:
@@ -266,6 +274,11 @@ def main(argv=None) -> dict:
     ap.add_argument("--kmeans", type=int, default=0, metavar="K",
                     help="also cluster the training dialogues' TF-IDF features with KMeans(K) and save the model "
                          "(2 .. 64; 0 = off)")
+    ap.add_argument("--bisecting-kmeans", type=int, default=0, metavar="K",
+                    help="also cluster the training dialogues' TF-IDF features with BisectingKMeans(K) and save the "
+                         "model (2 .. 64; 0 = off)")
+    ap.add_argument("--silhouette", action="store_true",
+                    help="add the ClusteringEvaluator silhouette to the --kmeans / --bisecting-kmeans report")
     Config.add_cli_args(ap)          # --num-trees, --max-depth, --vocab-size, --seed, --device, --config ...
     args = ap.parse_args(argv)
     cfg = Config.from_cli(args)
@@ -330,7 +343,13 @@ def main(argv=None) -> dict:
                 n_estimators=min(int(cfg.num_trees), 20), max_depth=int(cfg.max_depth))
         if args.kmeans:
             summary["KMeans"] = fit_kmeans_clusters(next(iter(models.values())).stages[:-1], args.kmeans, train_df,
-                                                    os.path.join(args.out_dir, "kmeans_model"), args.seed)
+                                                    os.path.join(args.out_dir, "kmeans_model"), args.seed,
+                                                    silhouette=args.silhouette)
+        if args.bisecting_kmeans:
+            summary["BisectingKMeans"] = fit_kmeans_clusters(
+                next(iter(models.values())).stages[:-1], args.bisecting_kmeans, train_df,
+                os.path.join(args.out_dir, "bisecting_kmeans_model"), args.seed, bisecting=True,
+                silhouette=args.silhouette)
         with open(os.path.join(args.out_dir, "results.json"), "w") as fh:
             json.dump({"metrics": summary, "word_stats": word_stats,
                        "split": [train_df.count(), val_df.count(), test_df.count()]}, fh, indent=2)

@@ -140,6 +140,31 @@ def kmeans_bytes(rows: int, nnz: int, k: int, num_features: int, value_bytes: in
         + 2.0 * num_features
 
 
+def bisecting_kmeans_bytes(rows: int, nnz: int, num_features: int, k: int = 64, value_bytes: int = 8) -> float:
+    """Peak bytes of a BisectingKMeans fit (models/bisecting.py) on one shard: a level of up to 32
+    splits is a pass of up to 64 centers, so ``K = min(64, 2 (k - 1))`` in the sums ``S`` (``8 K F``), the
+    children before and after the update (``8 Kp F`` twice) and their host copy's device upload (once
+    more), the 2-byte slot table, and per row the indptr, the weight, the int64 leaf position, the
+    int32 group and the int32 cluster and fp64 distance of the level's last pass."""
+    K = max(2, min(64, 2 * (int(k) - 1)))
+    kp = (K + 7) // 8 * 8
+    per_row = 8.0 + 8.0 + 8.0 + 4.0 + (4.0 + 8.0)
+    return (4.0 + value_bytes) * nnz + per_row * rows + 8.0 * K * num_features + 3 * 8.0 * kp * num_features \
+        + 2.0 * num_features
+
+
+def silhouette_bytes(rows: int, nnz: int, num_features: int, k: int, value_bytes: int = 8, want_rows: bool = False) -> float:
+    """Peak bytes of one ``ClusteringEvaluator`` evaluation (models/silhouette.py) on one shard: the CSR,
+    pass A's sums ``S`` (``8 K F``), the zero centers and the means (``8 Kp F`` each), the 2-byte slot table
+    and per row the indptr, the weight, the int64 prediction and its int32 copy, plus the fp64
+    coefficient when it is asked for."""
+    K = max(2, int(k))
+    kp = (K + 7) // 8 * 8
+    per_row = 8.0 + 8.0 + 8.0 + 4.0 + (8.0 if want_rows else 0.0)
+    return (4.0 + value_bytes) * nnz + per_row * rows + 8.0 * K * num_features + 2 * 8.0 * kp * num_features \
+        + 2.0 * num_features
+
+
 def rf_lanes_that_fit(rows: int, want: int, free_bytes: int, headroom: float = 0.5) -> int:
     """Trees in flight whose workspaces fit ``headroom`` of ``free_bytes`` (at least 1, at most
     ``want``): the cap models/tree.fit_forest applies before building its lanes."""
